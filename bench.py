@@ -8,6 +8,8 @@ train/stage_rl/trainer/sc_grpo_trainer.py:586) -> `SCGRPOEngine.step` -> AdamW, 
   python bench.py --gpus N --steps K --warmup W
       N > 1 without a torchrun environment: re-executes itself under `python -m torch.distributed.run --nproc-per-node N` (one rank per GPU,
       RCCL); under torchrun it checks WORLD_SIZE == N.
+  python bench.py ... --dump-outputs DIR
+      also writes what the last timed step computed as DIR/<name>.npy (rank 0; inputs and weights are seeded, so runs with the same arguments see the same inputs).
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
   roofline        : the launch that owns the step, named in `dominant` -- the rollout's decode replay (one hipGraph launch per generated token, HBM-bound: 56 % of the
@@ -152,7 +154,44 @@ def parse():
                     "--model llava_ov_7b, whose eager-attention autograd graph at 4019 positions x 28 layers does not fit the GPU box's 300 GiB memory cgroup")
     ap.add_argument("--check-noise", type=float, default=0.02, help="--check: element-wise relative noise policy = reference x (1 + noise)")
     ap.add_argument("--check-greedy-tokens", type=int, default=24, help="--check: greedy tokens compared between the hipGraph rollout and the oracle's KV-cached decode")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed in its LAST step as DIR/<name>.npy "
+                    "(float32 / float64, rank 0): the step's losses, completion ids, per-token log-probs of both models, KL, advantages, rewards, and a fixed, seeded "
+                    "sample of the updated parameters (bf16 weights and fp32 master copy) -- so that two builds can be compared output for output")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1 (the number of timed steps)")
+    return a
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+PARAM_SAMPLE = 1 << 20       # parameters in the --dump-outputs sample (the same seeded positions in every run of the same model)
+
+
+def param_sample(store, n=PARAM_SAMPLE, seed=0):
+    """A fixed, seeded sample of a ParamStore's flat parameter vector: positions, the bf16 weights the model computes with, and the fp32 master copy AdamW updates."""
+    idx = np.sort(np.random.default_rng(seed).integers(0, store.n_total, size=min(n, store.n_total)))
+    at = torch.from_numpy(idx).to(store.flat.device)
+    out = {"param_sample_index": idx, "param_sample_weights": store.flat[at].float().cpu().numpy()}
+    if getattr(store, "master", None) is not None:
+        out["param_sample_master"] = store.master[at].cpu().numpy()
+    return out
+
+
+def dump_outputs(path, arrays):
+    """DIR/<name>.npy per array: floating arrays as float32 (float64 stays float64), integer / boolean ones as float64 (exact for ids and positions)."""
+    conv = {}
+    for name, x in arrays.items():
+        if isinstance(x, torch.Tensor):
+            x = x.detach().float().cpu().numpy() if x.is_floating_point() else x.detach().cpu().numpy()
+        x = np.asarray(x)
+        conv[name] = x.astype(np.float64 if (x.dtype == np.float64 or not np.issubdtype(x.dtype, np.floating)) else np.float32)
+    total = sum(x.nbytes for x in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total / 2**20:.1f} MB exceeds the {DUMP_LIMIT_BYTES >> 20} MB limit")
+    os.makedirs(path, exist_ok=True)
+    for name, x in conv.items():
+        np.save(os.path.join(path, name + ".npy"), x)
+    print(f"[bench] --dump-outputs: {len(conv)} arrays, {total / 2**20:.1f} MB -> {path}", file=sys.stderr, flush=True)
 
 
 CANNED = [
@@ -910,6 +949,8 @@ def run_pa_sft(a, cfg, dev, rank, world):
     barrier()
     dt = time.perf_counter() - t0
     timer.enabled = False
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"loss": np.asarray([loss], dtype=np.float64), **param_sample(p)})
     if world > 1:
         import torch.distributed as dist
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -1288,12 +1329,22 @@ def main():
     alloc_trace = os.environ.get("IADR1_ALLOC_TRACE") == "1"     # who asks the device for memory inside the timed region (stderr; a diagnosis switch)
     if alloc_trace:
         torch.cuda.memory._record_memory_history(enabled="all", context="alloc", stacks="python", max_entries=200000)
+    last_out = {}
+    if a.dump_outputs:
+        # keep what the engine hands compute_loss (SCGRPOTrainer asks for return_outputs): the last step's log-probs, advantages, completion ids, ...
+        engine_step = eng.step
+
+        def recording_step(*args, **kw):
+            last_out["out"] = engine_step(*args, **kw)
+            return last_out["out"]
+        eng.step = recording_step
     timer.enabled = True
     if eng._rollout is not None:
         eng._rollout.decode_events = []
     t0 = time.perf_counter()
+    losses = None
     for _ in range(a.steps):
-        tr.training_step([rows(step_id)])
+        losses = tr.training_step([rows(step_id)])
         step_id += 1
     barrier()
     dt = time.perf_counter() - t0
@@ -1304,6 +1355,13 @@ def main():
            "alloc_retries": ms1.get("num_alloc_retries", 0),
            "device_allocs_in_timed_region": ms1.get("num_device_alloc", 0) - ms0.get("num_device_alloc", 0),
            "device_frees_in_timed_region": ms1.get("num_device_free", 0) - ms0.get("num_device_free", 0)}
+    if a.dump_outputs:        # read HERE, before the extra legs below run more steps on the same trainer
+        del eng.step
+        if rank == 0:
+            o = last_out["out"]
+            dump_outputs(a.dump_outputs, {"loss": np.asarray(losses, dtype=np.float64), "completion_ids": o["completion_ids"], "completion_mask": o["completion_mask"],
+                                          "logps": o["logps"], "ref_logps": o["ref_logps"], "kl": o["kl"], "advantages": o["advantages"],
+                                          "rewards_per_func": o["rewards_per_func"], **param_sample(eng.pol.p)})
     if alloc_trace:
         snap = torch.cuda.memory._snapshot()
         torch.cuda.memory._record_memory_history(enabled=None)

@@ -1934,8 +1934,12 @@ def test_weight_prefetcher_follows_the_decode_step_and_changes_no_token():
     """The opt-in persistent weight prefetcher (iadr1_weight_prefetch, iad-r1_amd/wprefetch.py; REF:637-683 is the loop it runs under): attached to a rollout it is
     paced by the progress marks the first kernel of every decoder layer stores -- it sees the (C - 1) x layers units and reads most of them, no timeout --,
     it returns when the rollout stores its sequence number in the stop word (twice in a row: the second launch starts from a clean progress word), and the tokens are
-    those of the rollout without it (it only reads).  3B widths, 2 layers, 16 sequences, C = 24; the prefetcher on an ordinary second stream."""
+    those of the rollout without it (it only reads).  3B widths, 2 layers, 16 sequences, C = 24; the prefetcher on a CU-masked stream of its own, as the engine
+    places it (overlap.cu_split): such a stream always gets a hardware queue of its own, while an ordinary pool stream may share the rollout stream's queue -- the
+    resident launch then holds the replays back until it times out.  (The stream stays alive, as hip.cu_mask_stream's streams do: the prefetcher's pinned status
+    buffer records an event on it when it is freed.)"""
     import dataclasses
+    from iadr1_amd import hip
     from iadr1_amd.wprefetch import WeightPrefetcher
     cfg = dataclasses.replace(VLMConfig.qwen25vl_3b(), num_hidden_layers=2, v_depth=2, v_fullatt=(1,))
     pol = ParamStore(cfg, DEV, trainable=True)
@@ -1952,7 +1956,7 @@ def test_weight_prefetcher_follows_the_decode_step_and_changes_no_token():
     main = torch.cuda.Stream()
     with torch.cuda.stream(main):
         want = eng.rollout(batch)
-        pf = WeightPrefetcher(eng.pol, torch.cuda.Stream(), 8, what=(), next_what=("qkv", "o"), lead=0)
+        pf = WeightPrefetcher(eng.pol, hip.cu_mask_stream(0, 8), 8, what=(), next_what=("qkv", "o"), lead=0)
         eng._rollout.wprefetch = pf
         for _ in range(2):
             got = eng.rollout(batch)

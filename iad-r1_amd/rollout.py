@@ -98,14 +98,6 @@ class Rollout:
         self.cos = torch.empty(N, D // 2, dtype=F32, device=dev)
         self.sin = torch.empty(N, D // 2, dtype=F32, device=dev)
         self.graph = None
-        # progress word of the decode step (step * layers + layer, stored by the first kernel of every decoder layer) and the weight prefetcher it paces
-        # (wprefetch.WeightPrefetcher, set by the owner; None: no marks in the captured step)
-        self.mark = torch.zeros(1, dtype=i32, device=dev)
-        self.pf_stop = torch.zeros(1, dtype=i32, device=dev)        # sequence number of the last finished rollout (the prefetcher's stop word)
-        self._pf_epoch = 0
-        self.wprefetch = None
-        self._marks_in_graph = False
-        self._marks_clean = True
         self._toks_host, self._toks_event = None, None
         self.trace = None           # training arena filled by the decode steps (generate(train_trace=...)); part of the captured graph
         self.decode_events = None   # bench.py sets a list: (start event, end event, decode steps, sum of prompt lengths over sequences) per call
@@ -117,20 +109,12 @@ class Rollout:
         e, c, P = self.e, self.e.cfg, self.e.p
         tr = self.trace      # None, or the training arena the step also fills (Rollout.generate(train_trace=...))
 
-        marks = self.wprefetch is not None
-        self._marks_in_graph = marks
-
-        def side(mark_layer=None, **kw):
+        def side(**kw):
             """iadr1_side_out_t for one launch of this step: rows base + s * stride + *step of the given arena tensors (None without a trace).
-            The structs are host memory read at launch time; they are kept in self._sides so that a re-capture builds them anew.
-            mark_layer: this launch opens decoder layer `mark_layer` -- with a weight prefetcher attached it also stores the step's progress mark."""
-            mk = dict(mark=self.mark, mark_mul=c.num_hidden_layers, mark_add=mark_layer) if (marks and mark_layer is not None) else {}
+            The structs are host memory read at launch time; they are kept in self._sides so that a re-capture builds them anew."""
             if tr is None:
-                if not mk:
-                    return None
-                so = ops.SideOut.make(self.step, 0, 0, **mk)
-            else:
-                so = ops.SideOut.make(self.step, tr["base"], tr["stride"], **kw, **mk)
+                return None
+            so = ops.SideOut.make(self.step, tr["base"], tr["stride"], **kw)
             self._sides.append(so)
             return so
 
@@ -145,10 +129,10 @@ class Rollout:
         for i in range(c.num_hidden_layers):
             b = f"layers.{i}."
             if not have_branch:      # layer 0 enters with the embedding rows (filled after the rollout)
-                ops.rmsnorm_fwd(self.x, P.w(b + "ln1"), c.rms_norm_eps, out=self.h, side=side(mark_layer=i, p1=T_("h1", i), p2=T_("rstd1", i)))
+                ops.rmsnorm_fwd(self.x, P.w(b + "ln1"), c.rms_norm_eps, out=self.h, side=side(p1=T_("h1", i), p2=T_("rstd1", i)))
             else:
                 ops.rmsnorm_fwd(None, P.w(b + "ln1"), c.rms_norm_eps, res=self.x, res_out=self.x, x32=self.part_d, out=self.h,
-                                side=side(mark_layer=i, p0=T_("x_in", i), p1=T_("h1", i), p2=T_("rstd1", i)))
+                                side=side(p0=T_("x_in", i), p1=T_("h1", i), p2=T_("rstd1", i)))
             if P.qkv_rope_packed:   # q|k|v projection + rotary + K/V cache append in one launch
                 ops.gemm_qkv_rope_kv(self.h, P.wpk(b + "qkv.w"), P.wpk_bias(b + "qkv.w"), self.qkv, self.cos, self.sin, self.slot, self.kc[i], self.vc[i], Hq, Hkv, D,
                                      side=side(p0=T_("qkv", i)))
@@ -240,8 +224,6 @@ class Rollout:
         mlp_on_shadow = bool(want_trace and shadow is not None and shadow.rebuilds_policy_mlp(c, N))
         if not want_trace and self.trace is not None:
             self.trace, self.graph = None, None
-        if (self.wprefetch is not None) != self._marks_in_graph:
-            self.graph = None      # the progress marks are part of the captured step
         lengths = plan.lengths
         # ---- page tables ------------------------------------------------------------------------------------
         next_page = 1  # page 0 is a scratch page for unused table entries
@@ -353,7 +335,6 @@ class Rollout:
             torch.cuda.synchronize()
             _t0 = _time.perf_counter()
             self._capture()  # warm-up + capture advance the state twice: restore it (K/V written meanwhile are rewritten by the real steps)
-            self._marks_clean = False
             for t, s_ in zip(state, saved):
                 t.copy_(s_)
             STATS["capture_seconds"] += _time.perf_counter() - _t0
@@ -364,18 +345,9 @@ class Rollout:
             gate = torch.cuda.Event()
             gate.record()                  # behind the sampling of token 0 (and the prefill): the reference's vision tower, prompt rows and first log-prob start now
             shadow.prompt_phase(gate)
-        if self.wprefetch is not None:     # one persistent launch for the whole rollout, on its own CU-masked stream; it polls the progress word the replays store
-            Lm = c.num_hidden_layers
-            if not self._marks_clean:      # (a capture / warm-up ran decode steps, or an exception cut a rollout short: the word must read 0 when the launch starts)
-                self.mark.zero_()
-                torch.cuda.current_stream().synchronize()
-                self._marks_clean = True
-            self._pf_epoch += 1
-            self.wprefetch.start(self.mark, 1 * Lm, (max_new - 1) * Lm + Lm - 1, self.pf_stop, self._pf_epoch)       # no stream dependency: see csrc/prefetch.hip
-            self._marks_clean = False
         # the CU-masked decode stream (and the host join that goes with it) only when something runs NEXT TO the replays: a rollout without the shadow pass
         # (SCGRPOTrainer.training_step's batched rollouts, step(completions=...), the evaluation harness) has nothing to hide behind the +0.2 ms per step
-        ds = self.decode_stream if (shadow is not None or self.wprefetch is not None) else None
+        ds = self.decode_stream if shadow is not None else None
         _outer = torch.cuda.current_stream()
         if ds is not None:                 # hand the rest of the rollout over to the CU-masked decode stream (the prefill above ran on the whole device)
             ds.wait_stream(_outer)
@@ -412,10 +384,6 @@ class Rollout:
                         STATS["eos_polls"] += 1
                         if int(self.done_host[k0]):
                             break
-            if self.wprefetch is not None:     # behind the last replay (the host joins this stream below): releases the prefetcher, also when EOS ended the rollout early,
-                self.pf_stop.fill_(self._pf_epoch)      # and leaves the progress word at 0 for the next rollout's launch
-                self.mark.zero_()
-                self._marks_clean = ds is not None      # (only the masked decode stream is joined on the host below)
             STATS["decode_steps"] += nsteps
             STATS["rollouts"] += 1
             if ev:
@@ -426,8 +394,6 @@ class Rollout:
             # stream
             if ds is not None:
                 torch.cuda.set_stream(_outer)
-            if self.wprefetch is not None and not self._marks_clean:
-                self.pf_stop.fill_(self._pf_epoch)      # (an exception cut the loop short: release the resident prefetch launch; the next start() zeroes the progress word)
         if ds is not None:
             # Join on the HOST: anything left pending on the outer stream's hardware queue while the replays run -- the dependency packet of `_outer.wait_stream(ds)`
             # (the host is hundreds of replays ahead), or a kernel polling the step counter -- costs every decode launch ~8 us when that queue happens to share a

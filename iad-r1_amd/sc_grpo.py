@@ -366,10 +366,6 @@ class SCGRPOEngine:
             self._rollout = None        # release the old pool before the new one is allocated
             split = self._cu_split(N)      # (the launcher configuration that goes with it is set by Rollout.generate for the duration of each call)
             self._rollout = Rollout(self.pol, N, grow, a.max_completion_length, max_prompts=Bp, use_graph=a.use_hip_graph, **split)
-            if split and self.__dict__.get("_wprefetch_stream") is not None:
-                # opt-in (IADR1_WPREFETCH_CUS): the NEXT layer's narrow projections (q|k|v, o: 18 MiB at the 3B widths) pulled into the memory-side cache while a layer runs
-                from .wprefetch import WeightPrefetcher, wanted_cus
-                self._rollout.wprefetch = WeightPrefetcher(self.pol, self._wprefetch_stream, wanted_cus(), what=(), next_what=("qkv", "o"), lead=0)
         c, st = self.cfg, self.pol.p
         # decode steps that also fill the training arena (no policy forward over the completions afterwards): needs the fused decode kernels that carry
         # the side outputs (q|k|v + rotary + cache append, persistent fused-SwiGLU gate|up GEMM)
@@ -411,8 +407,7 @@ class SCGRPOEngine:
         self._shadow_stream = None
         if n <= 0 or self.dev.type != "cuda" or not ChunkedRefPass.applicable(self.cfg, N, self.args.max_completion_length):
             return {}
-        from .wprefetch import wanted_cus
-        sp = cu_split(self.dev, n, self.ref.p.w("layers.0.gu.w"), prefetch_cus=wanted_cus())
+        sp = cu_split(self.dev, n, self.ref.p.w("layers.0.gu.w"))
         # one decision for the whole data-parallel job, taken once (the first rollout of a run, the same call on every rank: N and the completion length are the
         # launch configuration's, identical across ranks): a rank without a clean stream pair switches co-scheduling off for all of them
         agreed = self.__dict__.setdefault("_co_sched_agreed", {})
@@ -428,7 +423,6 @@ class SCGRPOEngine:
                 raise RuntimeError(f"IADR1_OVERLAP_CUS={n}: no stream pair on separate dispatch pipes was found; unset it (auto: sequential fallback) or set IADR1_OVERLAP_STRICT=0")
             return {}
         self._shadow_stream = sp[1]
-        self._wprefetch_stream = sp[3]
         return {"decode_cus": sp[2], "decode_stream": sp[0]}
 
     def _rollout_fuses_swiglu(self, N) -> bool:

@@ -135,13 +135,10 @@ class Engine:
         self.wgrad_tn_wide = False      # ops.gemm_tn_acc(wide=...): the owner sets it (sft.SFTEngine: True)
         # (which pool stream -- hardware queue -- the side stream is does not matter for two ordinary streams: PA-SFT 3B 356.4 - 358.4 ms per step over six choices)
         self.wgrad_stream = torch.cuda.Stream() if (self.dev.type == "cuda" and os.environ.get("IADR1_WGRAD_STREAM", "1") != "0") else None
-        self.keep_logits_bytes = 24 << 30
-        # lm_head + log-softmax + gather.  "fused" (default): the linear_logprob kernels -- logits never reach HBM, the backward recomputes them straight into
-        # dlogits; "logits": the two-step form (fp32 logit chunks + row kernels; a differentiated pass keeps its logits when they fit `keep_logits_bytes`).
-        # Measured on the 3B bench shape: 1261.9 (fused) vs 1263.2 ms per step, and 10 GB of kept logits less.  Policy and frozen reference always run the
-        # same form, so a policy that equals the reference has KL == 0 exactly (bit-equal log-probs).
-        self.head_mode = os.environ.get("IADR1_HEAD", "fused")
-        assert self.head_mode in ("fused", "logits"), self.head_mode
+        # lm_head + log-softmax + gather: the linear_logprob kernels -- logits never reach HBM, the backward recomputes them straight into dlogits, `lm_chunk` rows at
+        # a time.  (The two-step form -- fp32 logit chunks + logprob_rows / dlogits_rows, kept logits -- measured 1263.2 against 1261.9 ms per step on the 3B bench
+        # shape, with 10 GB of kept logits more; removed.)  Policy and frozen reference run the same launches, so a policy that equals the reference has KL == 0
+        # exactly (bit-equal log-probs).
         self._ws = {}
 
     def _workspace(self, key, shape, dtype):
@@ -1082,8 +1079,8 @@ class Engine:
         return ops.h2d(ptr, device), ops.h2d(order, device)
 
     def logprobs(self, hf: torch.Tensor, rows: torch.Tensor, targets: torch.Tensor, save: bool, dup=None, rows_host=None, precomputed=None):
-        """logp[r] = log_softmax(lm_head(hf[rows[r]]))[targets[r]]  (targets < 0 -> 0).  The [R,V] logits exist
-        only as fp32 chunks of `lm_chunk` rows.  `rows` may repeat a hidden row only where `dup` = (sel, dest, group) says so:
+        """logp[r] = log_softmax(lm_head(hf[rows[r]]))[targets[r]]  (targets < 0 -> 0), by one fused linear_logprob launch pair over all R rows (GEMM
+        epilogue -> (max, sum exp) per 64-column slice + target logit, then a per-row merge): the [R,V] logits never reach HBM.  `rows` may repeat a hidden row only where `dup` = (sel, dest, group) says so:
         entries rows[sel] all equal dest[group] (shared-prefix layout: the prompt's last token predicts the first token of
         every completion of its group); the backward sums their gradients.
         precomputed: (logp [R], lse [R]) of exactly these rows / targets, already produced by the same fused launch elsewhere (overlap.ChunkedRefPass._policy_head, on
@@ -1094,39 +1091,23 @@ class Engine:
         R = rows.numel()
         if precomputed is not None:
             logp, lse = precomputed
-            assert logp.numel() == R and lse.numel() == R and self.head_mode == "fused"
+            assert logp.numel() == R and lse.numel() == R
             ctx = None
             if save:
                 ptr, idx = self.scatter_plan(rows_host if rows_host is not None else rows.cpu().numpy(), hf.shape[0], self.dev)
-                ctx = {"hsel": hsel, "rows": rows, "targets": targets, "lse": lse, "T": hf.shape[0], "scatter": (ptr, idx), "logits": None}
+                ctx = {"hsel": hsel, "rows": rows, "targets": targets, "lse": lse, "T": hf.shape[0], "scatter": (ptr, idx)}
             return logp, ctx
         logp = torch.empty(R, dtype=F32, device=self.dev)
         lse = torch.empty(R, dtype=F32, device=self.dev)
-        V = W.shape[0]
-        # with `save`, the fp32 logits of all R rows are kept for the backward (10 GB for 16384 x 151936: nothing on a 288 GB part)
-        # instead of being recomputed chunk by chunk; without it only one chunk is ever alive
-        fused = self.head_mode == "fused"
-        # fused: one linear_logprob launch pair over all R rows (GEMM epilogue -> (max, sum exp) per 64-column slice + target logit, then a per-row merge)
-        keep = save and R * V * 4 <= self.keep_logits_bytes and not fused
-        lg_all = self._workspace("lm_logits_all", (R, V), F32) if keep else None
-        if fused:
-            need = ops.linear_logprob_ws_bytes(R, V)
-            ws = self._ws.get("lm_logprob_ws")
-            if ws is None or ws.numel() < need:                     # grow-only: the row count changes from batch to batch
-                ws = self._ws["lm_logprob_ws"] = torch.empty(need + need // 4, dtype=torch.uint8, device=self.dev)
-            ops.linear_logprob(hsel, W, targets, logp=logp, lse=lse, ws=ws)
-        else:
-            lg_buf = None if keep else self._workspace("lm_logits", (min(R, self.lm_chunk), V), F32)
-            for r0 in range(0, R, self.lm_chunk):
-                r1 = min(R, r0 + self.lm_chunk)
-                lg = ops.gemm_nt(hsel[r0:r1], W, out=lg_all[r0:r1] if keep else lg_buf[: r1 - r0])
-                lp, ls = ops.logprob_rows(lg, targets[r0:r1])
-                logp[r0:r1] = lp
-                lse[r0:r1] = ls
+        need = ops.linear_logprob_ws_bytes(R, W.shape[0])
+        ws = self._ws.get("lm_logprob_ws")
+        if ws is None or ws.numel() < need:                     # grow-only: the row count changes from batch to batch
+            ws = self._ws["lm_logprob_ws"] = torch.empty(need + need // 4, dtype=torch.uint8, device=self.dev)
+        ops.linear_logprob(hsel, W, targets, logp=logp, lse=lse, ws=ws)
         ctx = None
         if save:
             ptr, idx = self.scatter_plan(rows_host if rows_host is not None else rows.cpu().numpy(), hf.shape[0], self.dev)
-            ctx = {"hsel": hsel, "rows": rows, "targets": targets, "lse": lse, "T": hf.shape[0], "scatter": (ptr, idx), "logits": lg_all}
+            ctx = {"hsel": hsel, "rows": rows, "targets": targets, "lse": lse, "T": hf.shape[0], "scatter": (ptr, idx)}
         return logp, ctx
 
     def logprobs_backward(self, g: torch.Tensor, ctx) -> torch.Tensor:
@@ -1137,20 +1118,10 @@ class Engine:
         hsel, rows, targets, lse = ctx["hsel"], ctx["rows"], ctx["targets"], ctx["lse"]
         R, H = hsel.shape
         dhsel = torch.empty(R, H, dtype=BF16, device=self.dev)
-        V = W.shape[0]
-        nc = min(R, self.lm_chunk)
-        kept = ctx.get("logits")
-        fused = kept is None and self.head_mode == "fused"
-        lg_buf = None if kept is not None or fused else self._workspace("lm_logits", (nc, V), F32)
-        dl_buf = self._workspace("lm_dlogits", (nc, V), BF16)
+        dl_buf = self._workspace("lm_dlogits", (min(R, self.lm_chunk), W.shape[0]), BF16)
         for r0 in range(0, R, self.lm_chunk):
             r1 = min(R, r0 + self.lm_chunk)
-            n = r1 - r0
-            if fused:
-                dl = ops.linear_logprob_dlogits(hsel[r0:r1], W, targets[r0:r1], lse[r0:r1], g[r0:r1], out=dl_buf[:n])
-            else:
-                lg = kept[r0:r1] if kept is not None else ops.gemm_nt(hsel[r0:r1], W, out=lg_buf[:n])
-                dl = ops.dlogits_rows(lg, targets[r0:r1], lse[r0:r1], g[r0:r1], out=dl_buf[:n])
+            dl = ops.linear_logprob_dlogits(hsel[r0:r1], W, targets[r0:r1], lse[r0:r1], g[r0:r1], out=dl_buf[: r1 - r0])
             ops.gemm_nt(dl, WT, out=dhsel[r0:r1])
             ops.gemm_tn_acc(dl, hsel[r0:r1], self.p.g(name), wide=self.wgrad_tn_wide)          # dW_head += dl^T . h  (no [V, n] transposed copy of the logit gradients)
         # scatter back onto the token rows: dhf[t] = sum of the selected rows that read hidden row t (0 for rows nothing read)

@@ -75,7 +75,6 @@ def test_co_scheduling_host_logic(monkeypatch):
     monkeypatch.setenv("IADR1_OVERLAP_CUS", "-1")
     assert overlap.ChunkedRefPass.unmasked() and overlap.ChunkedRefPass.applicable(c3, 8, 48)
     assert overlap.ChunkedRefPass.rebuilds_policy_mlp(c3, 16) and not overlap.ChunkedRefPass.rebuilds_policy_mlp(c3, 8)
-    monkeypatch.delenv("IADR1_OVERLAP_TAIL", raising=False)
     p = overlap.ChunkedRefPass.__new__(overlap.ChunkedRefPass)
     p.steps, p.policy = 32, None
     assert p.boundaries(256) == set(range(32, 256, 32)) | {240} and p.boundaries(48) == {32}

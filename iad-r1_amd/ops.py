@@ -19,9 +19,6 @@ def _ld(x: torch.Tensor) -> int:
     return x.stride(0)
 
 
-_FUSE_SWIGLU = os.environ.get("IADR1_FUSE_SWIGLU", "1") != "0"
-
-
 def h2d(a, device):
     """Host array / CPU tensor -> device tensor through pinned memory, without blocking.  A pageable host-to-device copy synchronises the stream: the host
     would wait for everything it has enqueued so far, lose its run-ahead, and the GPU would idle while it catches up (index plans, targets, advantages are
@@ -77,14 +74,13 @@ def gemm_tn_acc(dy, x, out, wide=False):
     return gemm_nt(transpose(dy, pad_rows_to=8), transpose(x, pad_rows_to=8), out=out, accumulate=True)
 
 
-_SPLITK = os.environ.get("IADR1_GEMM_SPLITK", "1") != "0"
 _splitk_ws = {}
 
 
 def splitk_slices(M, N, K) -> int:
     """K slices for an accumulate-mode GEMM (weight gradient) whose 256 x 256 output tiles do not fill 256 CUs twice over: enough slices for >= 512 blocks, each
-    at least 1024 deep (16 K tiles: the prologue / epilogue of a tile stay below ~10 %); 1 = the plain kernel.  IADR1_GEMM_SPLITK=0 switches it off (A/B)."""
-    if not _SPLITK or M < 512 or N < 512 or N % 4 or K < 4096:
+    at least 1024 deep (16 K tiles: the prologue / epilogue of a tile stay below ~10 %); 1 = the plain kernel."""
+    if M < 512 or N < 512 or N % 4 or K < 4096:
         return 1
     tiles = ((M + 255) // 256) * ((N + 255) // 256)
     if tiles >= 448:
@@ -313,7 +309,7 @@ def gemm_swiglu(x, w_gu, gu_out=None, a_out=None, keep_gu=True):
     T, K = x.shape
     I = w_gu.shape[0] // 2
     a = a_out if a_out is not None else torch.empty(T, I, dtype=BF16, device=x.device)
-    if _FUSE_SWIGLU and T % 256 == 0 and I % 128 == 0 and (T // 256) * (I // 128) >= 192 and _ld(x) % 8 == 0:
+    if T % 256 == 0 and I % 128 == 0 and (T // 256) * (I // 128) >= 192 and _ld(x) % 8 == 0:
         gu = (gu_out if gu_out is not None else torch.empty(T, 2 * I, dtype=BF16, device=x.device)) if keep_gu else None
         gemm_swiglu_fused(x, w_gu, gu, a)
         return gu, a

@@ -65,8 +65,8 @@ class Rollout:
         self.x = torch.empty(N, H, dtype=BF16, device=dev)
         # GEMM inputs live in the decode-packed layout (ops.PackedAct: MFMA B-fragment order), written directly by their
         # producers (RMSNorm, decode attention, the fused SwiGLU epilogue) so that every X fragment load of the skinny GEMMs
-        # is one contiguous 1 KiB read instead of 16 half cache lines.  IADR1_DECODE_PACKED=0 keeps row-major (A/B switch).
-        self.packed = os.environ.get("IADR1_DECODE_PACKED", "1") != "0" and H % 32 == 0 and (Hq * D) % 32 == 0
+        # is one contiguous 1 KiB read instead of 16 half cache lines.
+        self.packed = H % 32 == 0 and (Hq * D) % 32 == 0
         self.fuse_swiglu = I % 64 == 0
         act = (lambda k: ops.PackedAct(N, k, dev)) if self.packed else (lambda k: torch.empty(N, k, dtype=BF16, device=dev))
         self.h = act(H)

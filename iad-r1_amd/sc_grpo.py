@@ -430,7 +430,7 @@ class SCGRPOEngine:
         c = self.cfg
         ncu = torch.cuda.get_device_properties(self.dev).multi_processor_count
         K, N2 = c.hidden_size, 2 * c.intermediate_size
-        return (self._rollout.fuse_swiglu and os.environ.get("IADR1_SKINNY_PERS", "1") != "0" and K % 256 == 0 and K // 256 in (4, 6, 8)
+        return (self._rollout.fuse_swiglu and K % 256 == 0 and K // 256 in (4, 6, 8)
                 and N2 % 128 == 0 and N2 // 32 >= 2 * ncu and N <= 256)
 
     # ---- loss + gradients for given completions ------------------------------------------------------------------

@@ -1113,8 +1113,6 @@ def test_decode_steps_fill_the_training_arena():
     that does run that forward: same tokens and rewards, loss and KL within the bf16 noise of decode-vs-training kernels, gradient cosine > 0.999."""
     import dataclasses
     import sys
-    if os.environ.get("IADR1_SKINNY_PERS", "1") == "0" or os.environ.get("IADR1_DECODE_PACKED", "1") == "0":
-        pytest.skip("the side outputs live in the persistent / fused decode kernels")
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import bench
     cfg = dataclasses.replace(VLMConfig.qwen25vl_3b(), num_hidden_layers=2, v_depth=2, v_fullatt=(1,))
@@ -1176,8 +1174,6 @@ def test_api_step_with_rollout_handover_matches_the_oracle(monkeypatch, overlap_
     import dataclasses
     import sys
     monkeypatch.setenv("IADR1_OVERLAP_CUS", overlap_cus)
-    if os.environ.get("IADR1_SKINNY_PERS", "1") == "0" or os.environ.get("IADR1_DECODE_PACKED", "1") == "0":
-        pytest.skip("the side outputs live in the persistent / fused decode kernels")
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from oracle import qwen25vl as oq
     from oracle import sc_grpo as og

@@ -10,6 +10,10 @@ train/stage_rl/trainer/sc_grpo_trainer.py:586) -> `SCGRPOEngine.step` -> AdamW, 
       RCCL); under torchrun it checks WORLD_SIZE == N.
   python bench.py ... --dump-outputs DIR
       also writes what the last timed step computed as DIR/<name>.npy (rank 0; inputs and weights are seeded, so runs with the same arguments see the same inputs).
+  python bench.py ... --full
+      after the timed steps, also runs what the headline does not need (one GPU only, each where it applies): the step in the reference's repeated-rows
+      layout (`repeated_rows_layout`), the two real-processor legs (`real_processor`), the leg at the reference scripts' shapes (`real_shapes`) and the CPU
+      baseline (`cpu_baseline`, 3B).  Without it those keys are null: a plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
   roofline        : the launch that owns the step, named in `dominant` -- the rollout's decode replay (one hipGraph launch per generated token, HBM-bound: 56 % of the
@@ -19,7 +23,7 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with extra objec
   roofline_gemm   : gemm_nt_256 / gemm_nt_128 (bf16 MFMA).  achieved = sum of algorithmic 2*M*N*K over its launches in the timed region / the length of the UNION
                     of their HIP-event intervals on the launch streams (weight-gradient GEMMs overlap the dgrad chain on a side stream; the per-launch-sum
                     figure is printed beside it).
-  cpu_baseline    : the CPU oracle (oracle/qwen25vl.py, kind "port") running the components of one B=1 x G=8 step -- vision tower, prefill,
+  cpu_baseline    : (--full) the CPU oracle (oracle/qwen25vl.py, kind "port") running the components of one B=1 x G=8 step -- vision tower, prefill,
                     KV-cached greedy decode steps, reference forward, policy forward+backward, head -- at full 3B width on this box's host
                     cores, each timed on a bounded sample and multiplied by its count in the step (layers x 36, blocks x 32, decode steps x 255).
 """
@@ -131,19 +135,22 @@ def parse():
     ap.add_argument("--prompt-len", type=int, default=512)
     ap.add_argument("--gen-len", type=int, default=256)
     ap.add_argument("--micro-batch", type=int, default=0, help="sequences per ref/policy pass; 0 = 64 (3B) / 32 (7B: 20480-token activations of 28 wide layers do not fit next to the fp32 optimizer state)")
-    ap.add_argument("--no-repeated-rows-leg", action="store_true", help="skip the extra (untimed) step in the reference's repeated-prompt-rows layout")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run what the headline does not need: the repeated-rows, real-processor and "
+                    "real-shapes legs and the CPU baseline (each can be left out with its --no-* option); without it a run only sets up, warms up, times --steps "
+                    "steps, writes --dump-outputs and prints its line")
+    ap.add_argument("--no-repeated-rows-leg", action="store_true", help="--full: skip the extra (untimed) step in the reference's repeated-prompt-rows layout")
     ap.add_argument("--workload", default="sc_grpo", choices=["sc_grpo", "pa_sft"], help="sc_grpo = the north-star SC-GRPO step (default); pa_sft = BASELINE config 2 (PA-SFT, bs 16, 448^2 image, 512 prompt + 256 supervised tokens)")
     ap.add_argument("--sft-batch", type=int, default=16)
     ap.add_argument("--gradient-checkpointing", default=None, choices=["off", "auto", "on"], help="decoder activation recompute policy of the step (the reference scripts' "
                     "--gradient_checkpointing true = auto): lets e.g. --model 7b run one 64-sequence micro-batch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-real-processor-legs", action="store_true", help="skip the two extra (untimed for `value`) loops that feed uint8 images through the HF image processor inside the step")
-    ap.add_argument("--no-real-shapes-leg", action="store_true", help="skip the (untimed for `value`) leg at the reference scripts' shapes: B=1 x G=4, accum 2, ragged prompts, EOS live, 512 tokens")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-real-processor-legs", action="store_true", help="--full: skip the two extra (untimed for `value`) loops that feed uint8 images through the HF image processor inside the step")
+    ap.add_argument("--no-real-shapes-leg", action="store_true", help="--full: skip the (untimed for `value`) leg at the reference scripts' shapes: B=1 x G=4, accum 2, ragged prompts, EOS live, 512 tokens")
     ap.add_argument("--real-shapes-steps", type=int, default=4)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--cpu-full-step", action="store_true", help="run the oracle's REAL B = 1 x G SC-GRPO step once at full 3B size on the host cores (about 6 minutes, "
-                    "~130 GB of host memory; no GPU work) and print its JSON record -- the committed record is the newest profiles/rNN_cpu_full_step.json (round 6: r06); the default run's cpu_baseline "
+                    "~130 GB of host memory; no GPU work) and print its JSON record -- the committed record is the newest profiles/rNN_cpu_full_step.json (round 6: r06); a --full run's cpu_baseline "
                     "stays the bounded component sample")
     ap.add_argument("--launch-check", action="store_true", help="only the N-rank launch contract, no GPU work: respawn under torch.distributed.run when needed, assert WORLD_SIZE == --gpus, "
                     "rendezvous over gloo on 127.0.0.1, max-reduce a per-rank value, ONE JSON line from rank 0 (what tests/test_ddp_gloo.py runs on CPU)")
@@ -1282,9 +1289,12 @@ def main():
     N = a.prompts * a.group
     # inputs are generated and made resident in HBM BEFORE the timed region (the processor's fp32 patches stay fp32: the bf16 cast is part of the step)
     batches = []
-    real_legs = world == 1 and not llava and not a.no_real_processor_legs and a.prompt_len >= 261
+    real_legs = a.full and world == 1 and not llava and not a.no_real_processor_legs and a.prompt_len >= 261
     leg_steps = min(a.steps, 4)       # the two real-processor legs are bounded: they are a comparison beside `value`, not the timed region
-    for step_id in range(a.warmup + a.steps + 1 + (2 * (leg_steps + 1) + 1 if real_legs else 0)):
+    n_batches = a.warmup + a.steps
+    if a.full:      # the repeated-rows leg's step, then the real-processor legs' steps
+        n_batches += 1 + (2 * (leg_steps + 1) + 1 if real_legs else 0)
+    for step_id in range(n_batches):
         if llava:
             b = synth_batch_llava(cfg, a.prompts, 253, seed=1234 + 7919 * rank + step_id)
             bb = {"input_ids": torch.from_numpy(b["input_ids"]), "attention_mask": torch.from_numpy(b["attention_mask"]), "pixel_values": b["pixel_values"].to(dev)}
@@ -1409,7 +1419,7 @@ def main():
     # one extra step OUTSIDE the timed region in the reference's own layout (every prompt repeated in all G rows of its group,
     # IADR1_SHARE_PREFIX=0) so the line also says what the dedup of the prompt tokens is worth; N=1 only
     repeated = None
-    if world == 1 and not a.no_repeated_rows_leg and eng.args.share_prefix and a.group > 1:
+    if a.full and world == 1 and not a.no_repeated_rows_leg and eng.args.share_prefix and a.group > 1:
         try:
             eng.args.share_prefix, eng.args.micro_batch_seqs = False, min(a.micro_batch, 32)
             tr.training_step([rows(step_id)])          # buffers of this layout
@@ -1432,7 +1442,7 @@ def main():
         except Exception as exc:
             real = {"error": repr(exc)[:300]}
     shapes = None
-    if world == 1 and a.model in ("3b", "7b", "qwen2vl_2b", "tiny") and not a.no_real_shapes_leg and not llava:
+    if a.full and world == 1 and a.model in ("3b", "7b", "qwen2vl_2b", "tiny") and not a.no_real_shapes_leg and not llava:
         timer.enabled = False
         try:
             shapes = real_shapes_leg(tr, cfg, dev, a.real_shapes_steps)
@@ -1525,7 +1535,7 @@ def main():
         out["roofline"] = dict(out["roofline_decode"] if dom == "decode" else out["roofline_gemm"])
         out["roofline"]["dominant"] = dom
         out["roofline"]["share_of_step"] = {"decode_replays": dec_frac, "gemm_family": gemm_frac}
-        if not a.no_cpu_baseline and a.model == "3b" and world == 1:     # rank 0 at N = 1 only: the other ranks of a multi-GPU run would sit in the closing barrier
+        if a.full and not a.no_cpu_baseline and a.model == "3b" and world == 1:     # rank 0 at N = 1 only: the other ranks of a multi-GPU run would sit in the closing barrier
             live = cpu_baseline(D3, a.cpu_seconds, P=a.prompt_len, C=a.gen_len, G=a.group)
             out["cpu_baseline"] = live
             try:

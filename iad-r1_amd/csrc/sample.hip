@@ -163,6 +163,34 @@ __device__ __forceinline__ int eff_k(const SampleArgs& p) {
     return min(min(p.top_k > 0 ? p.top_k : MAXK, MAXK), p.V);
 }
 
+// The single-thread tail of stage 2: softmax over the n rank-sorted candidates in sval (weights left in w), top-p cut, inverse-CDF draw.  Returns the
+// RANK of the pick.  One function for both stage-2 kernels: iadr1_sample_logp's ids are bit-equal to iadr1_sample_topk_topp's because they are this code.
+__device__ __forceinline__ int topk_topp_pick(const SampleArgs& p, int row, const float* sval, float* w, int n) {
+    const float invT = 1.f / p.temperature;
+    const float mx = sval[0] * invT;
+    float tot = 0.f;
+    for (int j = 0; j < n; ++j) { const float e = __expf(sval[j] * invT - mx); w[j] = e; tot += e; }
+    // top-p on the top-k-renormalised distribution: keep j while the mass ranked before it is < top_p
+    float before = 0.f, kept = 0.f;
+    int nk = 0;
+    for (int j = 0; j < n; ++j) {
+        if (j > 0 && before >= p.top_p * tot) break;
+        kept += w[j];
+        before += w[j];
+        ++nk;
+    }
+    const uint32_t step = p.step_ptr ? *p.step_ptr : p.step;
+    const unsigned long long sd = p.seed_ptr ? *p.seed_ptr : (((unsigned long long)p.seed_hi << 32) | p.seed_lo);
+    const float u = philox_uniform((uint32_t)sd, (uint32_t)(sd >> 32), (uint32_t)row, step) * kept;
+    float cum = 0.f;
+    int pick = nk - 1;
+    for (int j = 0; j < nk; ++j) {
+        cum += w[j];
+        if (cum > u) { pick = j; break; }
+    }
+    return pick;
+}
+
 __global__ __launch_bounds__(NT) void sample_stage1(SampleArgs p) {
     __shared__ int hist[2048];
     __shared__ int sh_i[8];
@@ -225,30 +253,201 @@ __global__ __launch_bounds__(NT) void sample_stage2(SampleArgs p) {
         sidx[rank] = id;
     }
     __syncthreads();
+    if (t == 0) p.out[row] = sidx[topk_topp_pick(p, row, sval, cval, n)];
+}
+
+// ---- iadr1_sample_logp: the same sampler + whole-vocabulary sampling (top_k <= 0) + the log-prob of the pick ------------------------------------
+// Both need the softmax normaliser of the WHOLE row.  Stage 1 holds its slice in registers anyway: it also reduces it to
+//   (m1, s1) = (max x, sum exp(x - m1))                 temperature 1, nothing filtered or suppressed: what the loss scores (iadr1_logprob_rows)
+//   (mT, sT) = (max x, sum exp((x - mT) / T))           suppressed token excluded; only for top_k <= 0
+// four floats per (row, chunk) behind the candidate lists.  Stage 2 merges the NCHUNK partials with one wave (fixed shuffle trees, no atomics on floats).
+// Whole vocabulary: an inclusive scan of the chunk masses in chunk order finds the chunk that holds u * total, that ONE slice is read again and an
+// exclusive block scan of the per-thread sums (thread t owns contiguous ids, as in stage 1) finds the id.  Summation tree of a weight, all fixed:
+// <= ITEMS serial adds in the thread, 6 shuffle levels in the wave, 3 adds over the waves (stage 1: the chunk mass; stage 2 again: the position in
+// the chunk), 6 shuffle levels over the chunks: at most 2 * (20 + 6 + 3) + 6 = 64 fp32 additions deep.
+struct LogpArgs {
+    float* part;        // scratch [B][NCHUNK][4]: m1, s1, mT, sT
+    float* logp;        // optional [B, ld] log-probs, column = the step value
+    long long ld;
+    int cols;
+};
+
+__device__ __forceinline__ bool whole_vocab(const SampleArgs& p) { return p.top_k <= 0 && p.temperature > 0.f; }
+
+// inclusive scan over the lanes of a wave
+__device__ __forceinline__ float wave_incscan(float v) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float t = __shfl_up(v, o, WAVE);
+        if (lane >= o) v += t;
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(NT) void sample_logp_stage1(SampleArgs p, LogpArgs q) {
+    __shared__ int hist[2048];
+    __shared__ int sh_i[8];
+    __shared__ float sh_f[16];
+    __shared__ float oval[MAXK];
+    __shared__ int oidx[MAXK];
+    const int row = blockIdx.y, chunk = blockIdx.x, t = threadIdx.x;
+    const float* x = p.logits + (long long)row * p.ld;
+    const int csize = (p.V + NCHUNK - 1) / NCHUNK;
+    const int per = (csize + NT - 1) / NT;  // <= ITEMS
+    const int c0 = chunk * csize, c1 = min(p.V, c0 + csize);
+    float val[ITEMS];
+    int idx[ITEMS];
+    float xs = -INFINITY;   // the suppressed token's own logit, if this thread holds it: it counts at temperature 1
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {
+        const int g = c0 + t * per + i;
+        const bool ok = i < per && g < c1;
+        idx[i] = ok ? g : -1;
+        const float v = ok ? x[g] : -INFINITY;
+        const bool sup = ok && g == p.suppress;
+        if (sup) xs = v;
+        val[i] = sup ? -INFINITY : v;
+    }
+    const bool wv = whole_vocab(p);
+    float mT = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) mT = fmaxf(mT, val[i]);
+    const float m1 = block_max<NT>(fmaxf(mT, xs), sh_f);
+    mT = block_max<NT>(mT, sh_f + 4);
+    const float invT = wv ? 1.f / p.temperature : 0.f;
+    float s1 = 0.f, sT = 0.f;
+    if (m1 > -INFINITY) {
+#pragma unroll
+        for (int i = 0; i < ITEMS; ++i) s1 += expf(val[i] - m1);      // (padding and the suppressed slot hold -inf: they add 0)
+        if (xs > -INFINITY) s1 += expf(xs - m1);
+    }
+    if (wv && mT > -INFINITY) {
+#pragma unroll
+        for (int i = 0; i < ITEMS; ++i) sT += expf((val[i] - mT) * invT);
+    }
+    s1 = block_sum<NT>(s1, sh_f + 8);
+    sT = block_sum<NT>(sT, sh_f + 12);
     if (t == 0) {
+        float* o = q.part + ((long long)row * NCHUNK + chunk) * 4;
+        o[0] = m1; o[1] = s1; o[2] = mT; o[3] = sT;
+    }
+    if (wv) return;     // no candidate lists: stage 2 draws from the chunk masses
+    const int K = eff_k(p);
+    const int n = block_topk<ITEMS>(val, idx, K, hist, sh_i, oval, oidx);
+    float* cv = p.cand_val + ((long long)row * NCHUNK + chunk) * MAXK;
+    int* ci = p.cand_idx + ((long long)row * NCHUNK + chunk) * MAXK;
+    if (t < MAXK) {
+        cv[t] = t < n ? oval[t] : -INFINITY;
+        ci[t] = t < n ? oidx[t] : -1;
+    }
+}
+
+__global__ __launch_bounds__(NT) void sample_logp_stage2(SampleArgs p, LogpArgs q) {
+    __shared__ int hist[2048];
+    __shared__ int sh_i[8];
+    __shared__ float sh_f[8];
+    __shared__ float cval[MAXK];
+    __shared__ int cidx[MAXK];
+    __shared__ float sval[MAXK];
+    __shared__ int sidx[MAXK];
+    __shared__ float sraw[MAXK];
+    constexpr int NI = NCHUNK * MAXK / NT;
+    const int row = blockIdx.x, t = threadIdx.x, lane = t & 63;
+    const float* x = p.logits + (long long)row * p.ld;
+    const uint32_t step = p.step_ptr ? *p.step_ptr : p.step;    // read once, at entry: the Philox counter and the log-prob column
+    float* lp = (q.logp != nullptr && step < (uint32_t)q.cols) ? q.logp + (long long)row * q.ld + step : nullptr;
+    // every wave merges the NCHUNK partials for itself (lane = chunk; the same instructions on the same data: the same bits in all four waves)
+    const bool have = lane < NCHUNK;
+    const float* pr = q.part + ((long long)row * NCHUNK + (have ? lane : 0)) * 4;
+    const float m1 = have ? pr[0] : -INFINITY, s1 = have ? pr[1] : 0.f;
+    const float M1 = wave_max(m1);
+    const float lse = M1 + logf(wave_sum(m1 > -INFINITY ? s1 * expf(m1 - M1) : 0.f));
+    if (whole_vocab(p)) {
         const float invT = 1.f / p.temperature;
-        const float mx = sval[0] * invT;
-        float tot = 0.f;
-        for (int j = 0; j < n; ++j) { const float e = __expf(sval[j] * invT - mx); cval[j] = e; tot += e; }
-        // top-p on the top-k-renormalised distribution: keep j while the mass ranked before it is < top_p
-        float before = 0.f, kept = 0.f;
-        int nk = 0;
-        for (int j = 0; j < n; ++j) {
-            if (j > 0 && before >= p.top_p * tot) break;
-            kept += cval[j];
-            before += cval[j];
-            ++nk;
-        }
-        const uint32_t step = p.step_ptr ? *p.step_ptr : p.step;
+        const float mT = have ? pr[2] : -INFINITY, sT = have ? pr[3] : 0.f;
+        const float MT = wave_max(mT);
+        const float mass = mT > -INFINITY ? sT * expf((mT - MT) * invT) : 0.f;
+        const float inc = wave_incscan(mass);
+        const float total = __shfl(inc, NCHUNK - 1, WAVE);
         const unsigned long long sd = p.seed_ptr ? *p.seed_ptr : (((unsigned long long)p.seed_hi << 32) | p.seed_lo);
-        const float u = philox_uniform((uint32_t)sd, (uint32_t)(sd >> 32), (uint32_t)row, step) * kept;
-        float cum = 0.f;
-        int pick = nk - 1;
-        for (int j = 0; j < nk; ++j) {
-            cum += cval[j];
-            if (cum > u) { pick = j; break; }
+        const float target = philox_uniform((uint32_t)sd, (uint32_t)(sd >> 32), (uint32_t)row, step) * total;
+        // first chunk whose inclusive mass exceeds the target; rounding may leave none: then the last chunk that has any mass
+        const unsigned long long hit = __ballot(have && inc > target), any = __ballot(have && mass > 0.f);
+        const int chunk = hit ? (int)__builtin_ctzll(hit) : (any ? 63 - (int)__builtin_clzll(any) : 0);
+        const float rest = target - (__shfl(inc, chunk, WAVE) - __shfl(mass, chunk, WAVE));     // what is left of the target inside the chunk
+        const int csize = (p.V + NCHUNK - 1) / NCHUNK;
+        const int per = (csize + NT - 1) / NT;
+        const int c0 = chunk * csize, c1 = min(p.V, c0 + csize);
+        float w[ITEMS];
+        float ts = 0.f;
+#pragma unroll
+        for (int i = 0; i < ITEMS; ++i) {
+            const int g = c0 + t * per + i;
+            const bool ok = i < per && g < c1 && g != p.suppress;      // (g < c1 <= V: the re-read stays inside the row)
+            w[i] = ok ? expf((x[g] - MT) * invT) : 0.f;
+            ts += w[i];
         }
+        // exclusive block scan of the thread sums, in id order
+        const float winc = wave_incscan(ts);
+        if (t == 0) { sh_i[0] = 0x7fffffff; sh_i[1] = -1; }
+        if (lane == 63) sh_f[t >> 6] = winc;
+        __syncthreads();
+        float cum = winc - ts;
+        for (int i = 0; i < (t >> 6); ++i) cum += sh_f[i];
+        int first = 0x7fffffff, last = -1;      // first id whose inclusive weight exceeds `rest`; last id of the chunk with any weight (rounding fallback)
+#pragma unroll
+        for (int i = 0; i < ITEMS; ++i) {
+            cum += w[i];
+            if (w[i] > 0.f) {
+                const int g = c0 + t * per + i;
+                last = g;
+                if (cum > rest && first == 0x7fffffff) first = g;
+            }
+        }
+        if (first != 0x7fffffff) atomicMin(&sh_i[0], first);
+        if (last >= 0) atomicMax(&sh_i[1], last);
+        __syncthreads();
+        if (t == 0) {
+            const int pick = sh_i[0] != 0x7fffffff ? sh_i[0] : max(sh_i[1], 0);
+            p.out[row] = pick;
+            if (lp) *lp = x[pick] - lse;
+        }
+        return;
+    }
+    const float* cv = p.cand_val + (long long)row * NCHUNK * MAXK;
+    const int* ci = p.cand_idx + (long long)row * NCHUNK * MAXK;
+    float val[NI];
+    int idx[NI];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        idx[i] = ci[t * NI + i];
+        val[i] = cv[t * NI + i];
+    }
+    const int K = eff_k(p);
+    const int n = block_topk<NI>(val, idx, K, hist, sh_i, cval, cidx);
+    if (p.temperature <= 0.f) {
+        if (t == 0) {
+            const int pick = n > 0 ? cidx[0] : 0;
+            p.out[row] = pick;
+            if (lp) *lp = x[pick] - lse;
+        }
+        return;
+    }
+    if (t < n) {
+        const float v = cval[t];
+        const int id = cidx[t];
+        int rank = 0;
+        for (int j = 0; j < n; ++j) rank += (cval[j] > v) || (cval[j] == v && cidx[j] < id);
+        sval[rank] = v;
+        sidx[rank] = id;
+        sraw[rank] = x[id];     // every candidate's own logit, fetched by its thread: the serial tail below reads LDS only
+    }
+    __syncthreads();
+    if (t == 0) {
+        const int pick = topk_topp_pick(p, row, sval, cval, n);
         p.out[row] = sidx[pick];
+        if (lp) *lp = sraw[pick] - lse;
     }
 }
 
@@ -269,4 +468,25 @@ extern "C" int iadr1_sample_topk_topp(const float* logits, long long ld, long lo
     hipLaunchKernelGGL(sample_stage1, dim3(NCHUNK, B), dim3(NT), 0, stream, p);
     hipLaunchKernelGGL(sample_stage2, dim3(B), dim3(NT), 0, stream, p);
     return iadr1_check_launch("sample_topk_topp");
+}
+
+extern "C" long long iadr1_sample_logp_workspace_bytes(int B) { return (long long)B * NCHUNK * (MAXK * 8 + 16); }
+
+extern "C" int iadr1_sample_logp(const float* logits, long long ld, long long* out, float* logp_out, long long ld_logp, int logp_cols, void* workspace, int B,
+                                 int V, float temperature, int top_k, float top_p, int suppress_token, unsigned long long seed, unsigned step,
+                                 const unsigned* step_ptr, const unsigned long long* seed_ptr, hipStream_t stream) {
+    IADR1_REQUIRE(top_p > 0.f && top_p <= 1.f, "sample_logp: top_p must be in (0,1]");
+    IADR1_REQUIRE(top_k > 0 || top_p == 1.f, "sample_logp: top_k <= 0 samples the whole vocabulary and takes top_p = 1 only (got %g): a nucleus over all V tokens is not built", (double)top_p);
+    IADR1_REQUIRE(B > 0 && V > 0 && workspace != nullptr, "sample_logp: empty problem or missing workspace (iadr1_sample_logp_workspace_bytes)");
+    IADR1_REQUIRE(V <= NCHUNK * NT * ITEMS, "sample_logp: V=%d exceeds the built maximum %d", V, NCHUNK * NT * ITEMS);
+    IADR1_REQUIRE(top_k <= MAXK, "sample_logp: top_k=%d exceeds the built maximum %d", top_k, MAXK);
+    IADR1_REQUIRE(logp_out == nullptr || (logp_cols > 0 && ld_logp >= logp_cols), "sample_logp: logp_out needs logp_cols > 0 and ld_logp >= logp_cols");
+    float* cv = (float*)workspace;
+    int* ci = (int*)(cv + (long long)B * NCHUNK * MAXK);
+    float* part = (float*)(ci + (long long)B * NCHUNK * MAXK);
+    SampleArgs p{logits, ld, out, cv, ci, B, V, temperature, top_p, top_k, suppress_token, (uint32_t)seed, (uint32_t)(seed >> 32), step, step_ptr, seed_ptr};
+    LogpArgs q{part, logp_out, ld_logp, logp_cols};
+    hipLaunchKernelGGL(sample_logp_stage1, dim3(NCHUNK, B), dim3(NT), 0, stream, p, q);
+    hipLaunchKernelGGL(sample_logp_stage2, dim3(B), dim3(NT), 0, stream, p, q);
+    return iadr1_check_launch("sample_logp");
 }

@@ -152,14 +152,16 @@ def write_accuracy(answers_json_path: str, normal_flag: str = "good", show_overk
 # device side
 # ---------------------------------------------------------------------------------------------------------------------------
 class GreedyGenerator:
-    """Batched greedy decoding of a checkpoint with the rollout engine (what vLLM does in the reference's eval scripts)."""
+    """Batched greedy decoding of a checkpoint with the rollout engine (what vLLM does in the reference's eval scripts).  temperature > 0: sampling from the
+    whole vocabulary (vLLM SamplingParams(temperature, top_p=1.0), vLLM_LLaVA_detect_format.py:203-205), seeded: batch k of a generator draws from seed + 7919 k."""
 
-    def __init__(self, cfg, store, max_new_tokens: int = 512):
+    def __init__(self, cfg, store, max_new_tokens: int = 512, temperature: float = 0.0, seed: int = 0):
         from .vlm import Engine
         if not getattr(store, "with_decode_pack", False):
             raise ValueError("GreedyGenerator needs a ParamStore built with with_decode_pack=True (trainer.load_checkpoint(..., with_decode_pack=True))")
         self.cfg, self.engine, self.max_new = cfg, Engine(store), max_new_tokens
         self._rollout = None
+        self.temperature, self.seed = float(temperature), int(seed)
 
     def generate(self, batch: dict) -> np.ndarray:
         """batch: input_ids / attention_mask [B, P] (left padded), pixel_values, image_grid_thw, images_per_prompt.
@@ -182,7 +184,11 @@ class GreedyGenerator:
             grow = max(P, r.max_prompt if r is not None else 0)
             self._rollout = r = None
             self._rollout = r = Rollout(e, B, grow, self.max_new, max_prompts=B, use_graph=True)
-        return r.generate(plan, img, 1, self.max_new, temperature=0.0, top_k=1, top_p=1.0, seed=0).cpu().numpy()
+        T = float(getattr(self, "temperature", 0.0))
+        if T <= 0.0:
+            return r.generate(plan, img, 1, self.max_new, temperature=0.0, top_k=1, top_p=1.0, seed=0).cpu().numpy()
+        k = self._batches_sampled = getattr(self, "_batches_sampled", -1) + 1
+        return r.generate(plan, img, 1, self.max_new, temperature=T, top_k=0, top_p=1.0, seed=int(getattr(self, "seed", 0)) + 7919 * k).cpu().numpy()
 
 
 def encode_prompts(processor, prompts, images, family: str):
@@ -264,9 +270,11 @@ def detect_main(family: str, argv=None):
     ap.add_argument("--data_path", type=str, default=os.environ.get("IADR1_TEST_DATA", "Industrial_test"))
     ap.add_argument("--json_path", type=str, default=None, help="default: data/Test/<test_dataset>_format.json")
     a = ap.parse_args(argv)
-    if getattr(a, "temperature", 0.0) != 0.0:
-        raise SystemExit("--temperature: only 0 (greedy -- what every reference Inference.sh runs) is built; vLLM's temperature > 0 with top_p = 1.0 samples the whole "
-                         "vocabulary, the rollout's sampler keeps at most 64 candidates (top-k 50 is the training setting)")
+    if getattr(a, "temperature", 0.0) < 0.0:
+        raise SystemExit("--temperature must be >= 0")
+    # --temperature T > 0 (vLLM_LLaVA_detect_format.py:37-39,203-205: SamplingParams(temperature=T, top_p=1.0)) samples the whole vocabulary with the rollout's sampler
+    # (iadr1_sample_logp, top_k = 0), seeded with that script's 6666 (:256).  vLLM's own random stream cannot be reproduced: the answers of a sampled run are
+    # reproducible here, run to run, but are not the reference's draws.
     from transformers import AutoProcessor
     from .trainer import load_checkpoint
     cfg, store = load_checkpoint(a.model_path, "cuda", trainable=False, with_decode_pack=True)
@@ -276,6 +284,7 @@ def detect_main(family: str, argv=None):
     if cfg.is_llava and hasattr(processor, "tokenizer"):
         processor.tokenizer.padding_side = "left"
     gen = GreedyGenerator(cfg, store, max_new_tokens=512)
+    gen.temperature, gen.seed = float(getattr(a, "temperature", 0.0)), 6666
     model_name = os.path.split(a.model_path.rstrip("/"))[-1] + ("_Similar_template" if a.similar_template else "")
     out_dir = f"result/{a.name}/{a.test_dataset}/"
     os.makedirs(out_dir, exist_ok=True)

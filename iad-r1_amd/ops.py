@@ -628,6 +628,28 @@ def sample(logits32, temperature, top_k, top_p, seed, step, suppress_token=-1, s
     return o
 
 
+_sample_logp_ws = {}
+
+
+def sample_logp(logits32, temperature, top_k, top_p, seed, step, suppress_token=-1, step_ptr=None, out=None, seed_ptr=None, logp_out=None, want_logp=True):
+    """iadr1_sample_logp: `sample` (bit-equal ids for top_k in 1..64) + whole-vocabulary sampling for top_k <= 0 (top_p must be 1) + the temperature-1,
+    unfiltered log-prob of every pick.  logp_out: [B, cols] fp32, written at column step (*step_ptr when given), untouched when that is >= cols; None with
+    want_logp: a fresh [B, 1] tensor is used (step must then be 0 and step_ptr None).  Returns (ids, logp_out or None)."""
+    B, V = logits32.shape
+    o = out if out is not None else torch.empty(B, dtype=torch.int64, device=logits32.device)
+    if logp_out is None and want_logp:
+        assert step_ptr is None and int(step) == 0, "sample_logp: give logp_out [B, cols] when the step (the column) is not 0"
+        logp_out = torch.zeros(B, 1, dtype=F32, device=logits32.device)
+    key = (B, logits32.device)
+    ws = _sample_logp_ws.get(key)
+    if ws is None:
+        ws = torch.empty(hip.lib().iadr1_sample_logp_workspace_bytes(B), dtype=torch.uint8, device=logits32.device)
+        _sample_logp_ws[key] = ws
+    hip.call("sample_logp", logits32, _ld(logits32), o, logp_out, _ld(logp_out) if logp_out is not None else 0, logp_out.shape[1] if logp_out is not None else 0, ws, B, V,
+             float(temperature), int(top_k), float(top_p), int(suppress_token), int(seed), int(step), step_ptr, seed_ptr)
+    return o, logp_out
+
+
 def rope_kv_store(qkv, cos, sin, slot, kcache, vcache, Hq, Hkv, D):
     hip.call("rope_kv_store", qkv, _ld(qkv), cos, sin, slot, kcache, vcache, qkv.shape[0], Hq, Hkv, D)
 

@@ -102,7 +102,8 @@ class Rollout:
         self.trace = None           # training arena filled by the decode steps (generate(train_trace=...)); part of the captured graph
         self.decode_events = None   # bench.py sets a list: (start event, end event, decode steps, sum of prompt lengths over sequences) per call
         self.seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.sampling = dict(temperature=0.9, top_k=50, top_p=0.9, suppress=-1, eos=c.eos_token_id, pad=c.pad_token_id)
+        self.sampling = dict(temperature=0.9, top_k=50, top_p=0.9, suppress=-1, eos=c.eos_token_id, pad=c.pad_token_id, logps=False)
+        self.logps = None           # [N, max_new] fp32 log-probs of the sampled tokens (generate(return_logps=True)): column = the step counter, like out_tokens
 
     # ---- one decode step (graph body) -------------------------------------------------------------------------
     def _decode_step(self):
@@ -171,7 +172,12 @@ class Rollout:
 
     def _sample_and_advance(self):
         s = self.sampling
-        ops.sample(self.logits, s["temperature"], s["top_k"], s["top_p"], 0, 0, suppress_token=s["suppress"], step_ptr=self.step, out=self.sampled, seed_ptr=self.seed_dev)
+        if s["logps"] or (s["top_k"] <= 0 and s["temperature"] > 0):
+            # iadr1_sample_logp: the whole-vocabulary draw and / or the log-prob of the pick; the default path below is the launch pair it has always been
+            ops.sample_logp(self.logits, s["temperature"], s["top_k"], s["top_p"], 0, 0, suppress_token=s["suppress"], step_ptr=self.step, out=self.sampled, seed_ptr=self.seed_dev,
+                            logp_out=self.logps if s["logps"] else None, want_logp=False)
+        else:
+            ops.sample(self.logits, s["temperature"], s["top_k"], s["top_p"], 0, 0, suppress_token=s["suppress"], step_ptr=self.step, out=self.sampled, seed_ptr=self.seed_dev)
         ops.decode_advance(self.sampled, self.cur_tok, self.out_tokens, self.pos, self.ctx_len, self.slot, self.block_table, self.finished, self.step, s["eos"], s["pad"],
                            all_done=self.all_done, inv_freq=self.e.inv_freq, cos=self.cos, sin=self.sin)
 
@@ -190,7 +196,7 @@ class Rollout:
         STATS["graph_captures"] += 1
 
     # ---- public ---------------------------------------------------------------------------------------------------
-    def generate(self, *args, **kw) -> torch.Tensor:
+    def generate(self, *args, **kw):
         """`_generate` with this thread's launcher configuration (iadr1_set_decode_cus: the CU count the persistent decode grids are sized for) set for the
         duration of the call only: whatever ends the call, later skinny-GEMM callers of this thread size their grids for the whole device again."""
         try:
@@ -200,9 +206,11 @@ class Rollout:
                 ops.hip.set_decode_cus(0)
 
     def _generate(self, plan: TextPlan, img_embeds, G: int, max_new: int, temperature=0.9, top_k=50, top_p=0.9, seed=0, suppress_eos=False,
-                  stop_at_eos=True, train_carry=None, train_trace=False, shadow=None) -> torch.Tensor:
+                  stop_at_eos=True, train_carry=None, train_trace=False, shadow=None, return_logps=False):
         """plan: the Bp left-padded prompts.  Returns completion ids [Bp*G, max_new] (prompt-major order: p0 x G,
         p1 x G, ...), pad after the first EOS.
+        top_k <= 0: the whole vocabulary (top_p must then be 1.0).  return_logps: returns (ids, logps) -- logps [Bp*G, max_new] fp32 on the device, the
+        temperature-1 unfiltered log-prob of every sampled token under the logits it was sampled from (iadr1_sample_logp), 0 after a sequence's first EOS.
         shadow: an overlap.ChunkedRefPass -- the frozen reference's teacher-forced pass over the tokens produced so far is enqueued on ITS stream every
         `shadow.steps` decode steps, behind one event per chunk (the caller reads shadow.logp after shadow.join())."""
         e, c = self.e, self.e.cfg
@@ -214,8 +222,16 @@ class Rollout:
         if dev.type == "cuda":
             ops.hip.set_decode_cus(self.decode_cus)      # this thread's launcher configuration (persistent grids) for the duration of the call: generate() resets it
         self.seed_dev.fill_(int(seed) & 0x7FFFFFFFFFFFFFFF)   # device-resident: a new seed per rollout does not invalidate the captured graph
+        if int(top_k) <= 0 and float(temperature) > 0 and float(top_p) != 1.0:
+            raise ValueError(f"top_k <= 0 samples the whole vocabulary and needs top_p == 1.0 (got {top_p}): a nucleus over all tokens is not built")
         sampling = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p),
-                        suppress=c.eos_token_id if suppress_eos else -1, eos=c.eos_token_id if stop_at_eos and not suppress_eos else -1, pad=c.pad_token_id)
+                        suppress=c.eos_token_id if suppress_eos else -1, eos=c.eos_token_id if stop_at_eos and not suppress_eos else -1, pad=c.pad_token_id,
+                        logps=bool(return_logps))
+        if return_logps:
+            if self.logps is None:
+                self.logps = torch.zeros(self.N, self.max_new, dtype=F32, device=dev)
+                self.graph = None      # (the buffer is a kernel argument of the captured sampler)
+            self.logps.zero_()         # columns the loop never reaches (every sequence finished early) read 0
         if sampling != self.sampling:
             self.sampling = sampling
             self.graph = None  # sampling parameters are kernel arguments frozen in the graph
@@ -330,6 +346,8 @@ class Rollout:
         # ---- decode ----------------------------------------------------------------------------------------------
         if self.use_graph and self.graph is None:
             state = (self.pos, self.ctx_len, self.slot, self.finished, self.step, self.cur_tok, self.out_tokens, self.cos, self.sin, self.all_done)
+            if return_logps:
+                state = state + (self.logps,)
             saved = [t.clone() for t in state]
             import time as _time
             torch.cuda.synchronize()
@@ -415,6 +433,12 @@ class Rollout:
             shadow.finish(nsteps + 1, None)        # (the current stream is ordered behind the last replay)
             if shadow.trace is not None:
                 print("[iadr1 overlap] side-stream phases (ms after the start of the decode loop):", shadow.report(), flush=True)
+        if return_logps:
+            lp = self.logps[:, :max_new].clone()
+            if sampling["eos"] >= 0:       # the sampler does not know `finished`: what it drew for a finished sequence is masked here, on the device
+                is_eos = (toks == sampling["eos"]).to(torch.int32)
+                lp.masked_fill_((is_eos.cumsum(1) - is_eos) > 0, 0.0)
+            return toks, lp
         return toks
 
     def tokens_host(self) -> np.ndarray:

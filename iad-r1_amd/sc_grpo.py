@@ -38,8 +38,11 @@ class GRPOArgs:
     max_completion_length: int = 256
     beta: float = 0.04
     temperature: float = 0.9
-    top_k: int = 50            # hard-coded in the reference (REF:353-358)
+    top_k: int = 50            # hard-coded in the reference (REF:353-358); <= 0: the whole vocabulary (needs top_p == 1.0, checked when the engine is built)
     top_p: float = 0.9
+    # the rollout also returns the log-prob of every token it sampled (temperature 1, unfiltered: the quantity the loss scores); the step's metrics gain
+    # rollout/logp_abs_diff_mean, rollout/logp_abs_diff_max and rollout/kl against the policy log-probs of the loss.  Nothing in the loss or the gradients changes.
+    rollout_logps: bool = False
     learning_rate: float = 1e-6
     weight_decay: float = 0.0
     adam_beta1: float = 0.9
@@ -311,7 +314,10 @@ class _nullcontext:
 
 class SCGRPOEngine:
     def __init__(self, cfg: VLMConfig, policy: ParamStore, ref: ParamStore, args: GRPOArgs, group=None):
+        if args.top_k <= 0 and args.top_p != 1.0:
+            raise ValueError(f"GRPOArgs.top_k <= 0 samples the whole vocabulary and needs top_p == 1.0 (got top_p = {args.top_p}): a nucleus over all tokens is not built")
         self.cfg, self.args = cfg, args
+        self.last_rollout_logps = None      # [N, C] device tensor of the last rollout when args.rollout_logps
         self.pol, self.ref = Engine(policy), Engine(ref)
         self.dev = policy.device
         self.reducer = GradReducer(policy, group)
@@ -389,7 +395,10 @@ class SCGRPOEngine:
                 print("[iadr1] sequential step: the frozen reference's pass runs after the rollout, on the whole device", file=sys.stderr, flush=True)
         toks = self._rollout.generate(plan, img_pol, a.num_generations, a.max_completion_length, temperature=0.0 if greedy else a.temperature,
                                       top_k=a.top_k, top_p=a.top_p, seed=a.seed + 1000003 * self.opt_step + 7919 * self.accum, suppress_eos=a.suppress_eos,
-                                      train_carry=train_carry, train_trace=trace, shadow=shadow)
+                                      train_carry=train_carry, train_trace=trace, shadow=shadow, return_logps=a.rollout_logps)
+        self.last_rollout_logps = None
+        if a.rollout_logps:
+            toks, self.last_rollout_logps = toks
         if shadow is not None:
             self.shadow_logps = shadow.logp
             self.shadow_policy_head = (shadow.pol_logp, shadow.pol_lse) if shadow.pol_logp is not None else None
@@ -435,11 +444,13 @@ class SCGRPOEngine:
 
     # ---- loss + gradients for given completions ------------------------------------------------------------------
     def loss_and_grads(self, batch, completions, rewards_per_func, backward: bool = True, last_micro_step: bool = True, vis=None, train_carry=None, defer_metrics: bool = False,
-                       ref_logps=None, policy_head=None):
+                       ref_logps=None, policy_head=None, rollout_logps=None):
         """completions: list of Bp*G id lists (prompt-major) or an [N,C] array already padded;
         rewards_per_func: [N, n_funcs] float tensor/array.  Accumulates gradients into policy.grad.
         ref_logps: [N, C] reference log-probs already computed for exactly these completions by the rollout's shadow pass (rollout(shadow_ref=True)): the
-        reference forward is then not run here; the shadow stream is joined right before the loss kernel reads them."""
+        reference forward is then not run here; the shadow stream is joined right before the loss kernel reads them.
+        rollout_logps: [N, >= C] log-probs the rollout's sampler returned for exactly these completions (rollout with args.rollout_logps): compared with the policy
+        log-probs computed here over the completion mask (metrics rollout/*, result "rollout_logps"); the loss does not read them."""
         a, c = self.args, self.cfg
         G = a.num_generations
         ids_p, mask_p = np.asarray(batch["input_ids"]), np.asarray(batch["attention_mask"])
@@ -564,18 +575,33 @@ class SCGRPOEngine:
             self.accum += 1
         st = advantages()
         metrics = {"completion_length": float(cmask.sum(1).mean()), "reward": float(st["rewards"].mean()), "reward_std": float(st["std"].mean())}
-        dev_means = torch.stack([row_loss.mean(), row_kl.mean()])       # one device -> host read for both
+        means = [row_loss.mean(), row_kl.mean()]
+        ro_lp = None
+        if rollout_logps is not None:
+            # sampled (the rollout's logits) vs scored (the policy forward of the loss) log-probs of the same tokens, over the completion mask; k3 estimator of
+            # KL(sampled || scored) in the form iadr1_grpo_loss uses for policy vs reference: exp(d) - d - 1 with d = scored - sampled
+            ro_lp = rollout_logps[:, :C].to(F32)
+            m_ = cmask_d.to(F32)
+            d_ = (logp_all - ro_lp) * m_
+            cnt = m_.sum().clamp(min=1.0)
+            means += [d_.abs().sum() / cnt, d_.abs().max(), ((torch.exp(d_) - d_ - 1.0) * m_).sum() / cnt]
+        dev_means = torch.stack(means)       # one device -> host read for all of them
 
         def finalize():
             lk = dev_means.tolist()
             metrics.update(loss=lk[0], kl=lk[1])
+            if ro_lp is not None:
+                metrics.update({"rollout/logp_abs_diff_mean": lk[2], "rollout/logp_abs_diff_max": lk[3], "rollout/kl": lk[4]})
             return metrics
         if defer_metrics:      # the caller enqueues more work (the optimizer) before it reads the two device-side means: no idle GPU while the host comes back from the sync
             metrics["finalize"] = finalize
         else:
             finalize()
-        return {"metrics": metrics, "logps": logp_all, "ref_logps": ref_all, "kl": kl_all, "advantages": st["adv"], "completion_mask": cmask,
-                "rewards_per_func": st["rpf"], "ids": ids, "mask": mask}
+        out = {"metrics": metrics, "logps": logp_all, "ref_logps": ref_all, "kl": kl_all, "advantages": st["adv"], "completion_mask": cmask,
+               "rewards_per_func": st["rpf"], "ids": ids, "mask": mask}
+        if ro_lp is not None:
+            out["rollout_logps"] = ro_lp
+        return out
 
     # ---- optimizer -------------------------------------------------------------------------------------------------
     def optimizer_step(self):
@@ -627,13 +653,14 @@ class SCGRPOEngine:
             return False
         return shadow_cus(self.cfg, n_seq, self.args.max_completion_length) > 0
 
-    def _step(self, batch, reward_fn, do_optimizer_step=True, last_micro_step=None, return_outputs=False, defer_metrics=False, completions=None):
+    def _step(self, batch, reward_fn, do_optimizer_step=True, last_micro_step=None, return_outputs=False, defer_metrics=False, completions=None, rollout_logps=None):
         """One SC-GRPO micro-step: vision tower -> group rollout -> rewards -> reference / policy passes + backward (-> optimizer).  This is the path
         `SCGRPOTrainer.compute_loss` (the reference's API, REF:586) runs and the one bench.py times.
         reward_fn(completion_ids: np.ndarray [N,C]) -> [N, n_funcs] rewards (decode + plugin functions live with the caller, which owns the tokenizer).
         last_micro_step (default: do_optimizer_step): the data-parallel gradient buckets leave from this call's backward.
         completions: [N, C] ids already rolled out for these prompts (SCGRPOTrainer.training_step rolls all micro-batches of an optimizer step out at once): no
         rollout here, the policy forward runs over the completions.
+        rollout_logps: with `completions`, the log-probs their rollout returned for these rows (args.rollout_logps; SCGRPOTrainer.training_step's batched rollouts).
         return_outputs: the whole loss_and_grads dict (log-probs, advantages, masks, ids, metrics) plus "completion_ids" instead of the metrics alone."""
         import time
         timing = os.environ.get("IADR1_TIMING") == "1"
@@ -658,6 +685,7 @@ class SCGRPOEngine:
         comp = self.rollout(batch, vis=vis, train_carry=carry, shadow_ref=True) if completions is None else np.asarray(completions)
         ref_lp = self.shadow_logps if completions is None else None
         pol_head = self.shadow_policy_head if completions is None else None
+        ro_lp = (self.last_rollout_logps if completions is None else rollout_logps) if self.args.rollout_logps else None
         t2 = mark()
         # rewards are computed on the host inside loss_and_grads, after the first forward passes are in the GPU queue (in the
         # phase-timing mode they are evaluated here so that they get their own column)
@@ -666,7 +694,7 @@ class SCGRPOEngine:
         self.last_step_traced = bool(carry and carry.get("traced"))     # the decode steps filled the completion rows of the training arena
         last = do_optimizer_step if last_micro_step is None else last_micro_step
         out = self.loss_and_grads(batch, comp, rewards, backward=True, last_micro_step=last, vis=vis, train_carry=carry, defer_metrics=defer_metrics or do_optimizer_step,
-                                  ref_logps=ref_lp, policy_head=pol_head)
+                                  ref_logps=ref_lp, policy_head=pol_head, rollout_logps=ro_lp)
         self.last_step_shadowed = ref_lp is not None
         t4 = mark()
         if do_optimizer_step:

@@ -41,6 +41,9 @@ class GRPOConfig:
     max_completion_length: int = 256
     beta: float = 0.04
     temperature: float = 0.9
+    top_k: int = 50                 # (vLLM SamplingParams of REF sc_grpo_trainer.py:353-358: top_k 50, top_p 0.9); <= 0: the whole vocabulary, needs top_p 1.0
+    top_p: float = 0.9
+    rollout_logps: bool = False     # log rollout/logp_abs_diff_mean|max and rollout/kl: sampled vs scored log-probs of the rollout's tokens (GRPOArgs.rollout_logps)
     learning_rate: float = 1e-6
     weight_decay: float = 0.0
     adam_beta1: float = 0.9
@@ -384,7 +387,7 @@ class SCGRPOTrainer:
             group = dist.group.WORLD
         self.engine = SCGRPOEngine(self.cfg, self.policy, self.ref, GRPOArgs(
             num_generations=args.num_generations, max_prompt_length=args.max_prompt_length, max_completion_length=args.max_completion_length,
-            beta=args.beta, temperature=args.temperature, learning_rate=args.learning_rate, weight_decay=args.weight_decay,
+            beta=args.beta, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, rollout_logps=args.rollout_logps, learning_rate=args.learning_rate, weight_decay=args.weight_decay,
             adam_beta1=args.adam_beta1, adam_beta2=args.adam_beta2, adam_epsilon=args.adam_epsilon, max_grad_norm=args.max_grad_norm,
             gradient_accumulation_steps=args.gradient_accumulation_steps, micro_batch_seqs=args.micro_batch_seqs, seed=args.seed,
             # under data parallelism the policy is "auto" even without the flag: it recomputes only where the static budget (which then reserves RCCL's buffers) is tight
@@ -445,7 +448,8 @@ class SCGRPOTrainer:
         return np.stack(cols, 1)
 
     # ---- reference API ---------------------------------------------------------------------------------------------
-    def compute_loss(self, model, inputs, return_outputs=False, num_items_in_batch=None, last_micro_step=True, _defer=False, _prepared=None, _batch=None, _completions=None):
+    def compute_loss(self, model, inputs, return_outputs=False, num_items_in_batch=None, last_micro_step=True, _defer=False, _prepared=None, _batch=None, _completions=None,
+                     _rollout_logps=None):
         """One SC-GRPO micro-step on `inputs` (list of dataset rows).  Returns the loss value; gradients are
         accumulated inside the engine (there is no autograd graph to hand back).
         _defer (training_step, last micro-batch): returns a callable that yields the loss once called -- the two device-side means (loss, KL) are then read
@@ -463,7 +467,7 @@ class SCGRPOTrainer:
         # the engine's whole micro-step (SCGRPOEngine.step): vision tower once per image, rollout whose prefill / decode steps double as the policy's
         # training forward when the micro-batch holds whole groups, rewards evaluated on the host while the reference pass is in the GPU queue
         out = self.engine.step(batch, lambda comp: self._rewards(inputs, comp), do_optimizer_step=False, last_micro_step=last_micro_step, return_outputs=True, defer_metrics=_defer,
-                               completions=_completions)
+                               completions=_completions, rollout_logps=_rollout_logps)
         m = out["metrics"]
         self._metrics["completion_length"].append(m["completion_length"])
         rp = out["rewards_per_func"].mean(0)
@@ -476,6 +480,9 @@ class SCGRPOTrainer:
             if "finalize" in m:
                 m.pop("finalize")()
             self._metrics["kl"].append(m["kl"])
+            for k in ("rollout/logp_abs_diff_mean", "rollout/logp_abs_diff_max", "rollout/kl"):
+                if k in m:
+                    self._metrics[k].append(m[k])
             return m["loss"]
         return finish if _defer else finish()
 
@@ -499,7 +506,7 @@ class SCGRPOTrainer:
         last one's backward) + clip / AdamW / weight-copy refresh.  What transformers.Trainer.training_step + the optimizer block of its inner loop do
         around the reference's compute_loss (TF:trainer.py:1892-1961, :1785); train() and bench.py both go through here."""
         last = len(micro_batches) - 1
-        ready = comps = None
+        ready = comps = lps = None
         rows_total = sum(len(mb) for mb in micro_batches) * self.args.num_generations
         if self.args.batch_rollouts and len(micro_batches) > 1 and rows_total <= 64:
             # (<= 64 sequences: one 64-row tile of the decode GEMMs -- beyond that a decode step streams the weights once per tile and batching buys nothing, while
@@ -511,13 +518,16 @@ class SCGRPOTrainer:
             if both is not None:
                 G = self.args.num_generations
                 toks = self.engine.rollout(both)
-                comps, r = [], 0
+                all_lp = self.engine.last_rollout_logps      # None unless GRPOConfig.rollout_logps
+                comps, lps, r = [], [], 0
                 for b in ready:
                     n = len(b["input_ids"]) * G
                     comps.append(trim_completions(toks[r: r + n], self.cfg.eos_token_id))
+                    lps.append(None if all_lp is None else all_lp[r: r + n, : comps[-1].shape[1]].contiguous())
                     r += n
         losses = [self.compute_loss(None, inputs, last_micro_step=(k == last), _defer=(k == last), _prepared=None if (prepared is None or ready is not None) else prepared[k],
-                                    _batch=None if ready is None else ready[k], _completions=None if comps is None else comps[k])
+                                    _batch=None if ready is None else ready[k], _completions=None if comps is None else comps[k],
+                                    _rollout_logps=None if comps is None else lps[k])
                   for k, inputs in enumerate(micro_batches)]
         self.engine.optimizer_step()
         losses[last] = losses[last]()       # the last micro-batch's loss / KL means are read after the optimizer launches are in the queue

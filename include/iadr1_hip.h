@@ -295,6 +295,21 @@ int iadr1_sample_topk_topp(const float* logits, long long ld, long long* out, vo
                            const unsigned* step_ptr, const unsigned long long* seed_ptr, iadr1_stream_t stream);
 /* step_ptr / seed_ptr: optional device-resident step counter / seed that replace the scalar arguments (a captured hipGraph freezes
  * kernel arguments: the rollout replays one graph for every decode step of every optimizer step). */
+/* iadr1_sample_logp: the same sampler, plus what vLLM returns beside the token ids and what its evaluation callers sample with.
+ *   top_k in 1..64: filter semantics, Philox stream and token ids of iadr1_sample_topk_topp, bit for bit (greedy, suppress_token, step_ptr, seed_ptr included).
+ *   top_k <= 0: the WHOLE vocabulary -- vLLM SamplingParams(temperature=T, top_p=1.0) of the LLaVA evaluation script
+ *     (REF:scripts/Inference/IAD-R1-Inference/vLLM_LLaVA_detect_format.py:37-39,203-205,252): one inverse-CDF draw over all V tokens in ascending id order with
+ *     the uniform philox(seed; row, step): the first id whose cumulative weight sum_{i <= id} exp((x_i - max) / T) exceeds u * total.  The summation tree is fixed
+ *     (run-to-run identical ids).  temperature == 0: greedy.  A suppressed token has weight 0.  top_p < 1 with top_k <= 0 is REFUSED (error through
+ *     iadr1_last_error): an exact nucleus over 152 k tokens is a different kernel (a full sort or a threshold search), not built here.
+ *   logp_out (may be NULL): logp_out[row * ld_logp + col] = log_softmax(logits[row, :])[picked] at temperature 1 over the full row, no filter, no suppression --
+ *     the quantity the loss scores (iadr1_logprob_rows; REF:...sc_grpo_trainer.py:505-513 _get_per_token_logps), vLLM's SamplingParams(logprobs=...).
+ *     col = *step_ptr (else step), the column iadr1_decode_advance writes in out_tokens; nothing is written when col >= logp_cols.
+ *   workspace: iadr1_sample_logp_workspace_bytes(B) bytes.  No allocation, no float atomics, no host sync: legal under hipGraph capture. */
+long long iadr1_sample_logp_workspace_bytes(int B);
+int iadr1_sample_logp(const float* logits, long long ld, long long* out, float* logp_out, long long ld_logp, int logp_cols, void* workspace, int B,
+                      int V, float temperature, int top_k, float top_p, int suppress_token, unsigned long long seed, unsigned step,
+                      const unsigned* step_ptr, const unsigned long long* seed_ptr, iadr1_stream_t stream);
 
 /* ---- device-resident rollout bookkeeping (one decode step = a fixed, graph-replayable launch sequence) ------
  * rope_table: cos/sin [B, half] for the current text positions (TF:1165-1176: pos = kv_len + rope_delta).

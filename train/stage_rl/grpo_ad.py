@@ -79,6 +79,10 @@ def build_parser():
     p.add_argument("--max_completion_length", type=int, default=256)
     p.add_argument("--beta", type=float, default=0.04)
     p.add_argument("--temperature", type=float, default=0.9)
+    p.add_argument("--top_k", type=int, default=50, help="rollout sampler (the reference hard-codes 50); <= 0: the whole vocabulary, needs --top_p 1.0")
+    p.add_argument("--top_p", type=float, default=0.9)
+    p.add_argument("--rollout_logps", nargs="?", default=False, const=True, type=lambda v: str(v).lower() in ("1", "true", "yes"),
+                   help="log rollout/logp_abs_diff_mean|max and rollout/kl: the sampler's log-probs of the tokens it drew against the loss's policy log-probs")
     p.add_argument("--learning_rate", type=float, default=1e-6)
     p.add_argument("--weight_decay", type=float, default=0.0)
     p.add_argument("--max_grad_norm", type=float, default=1.0)

@@ -181,40 +181,27 @@ def gemm_skinny(x, wp, N, bias=None, out=None, out_dtype=BF16, ksplit=1, swiglu=
     x may be a PackedAct.  ksplit > 1: `out` is fp32 [ksplit, M, N] partial slabs to be summed by rmsnorm_fwd(x32=...)."""
     M, K = x.shape
     xb, ldx = _xarg(x)
-    dev = xb.device
-    if isinstance(wp, tuple):       # (FP8 pack, per-row scales): ops.pack_weight_fp8 -- the opt-in FP8 weight stream of the rollout
-        w8, wscale = wp
-        assert w8.dtype == torch.uint8 and w8.numel() == N * K and wscale.numel() == N and side is None
-        if swiglu:
-            out = out if out is not None else torch.empty(M, N // 2, dtype=BF16, device=dev)
-            ob, ldo = _xarg(out)
-            hip.call("gemm_skinny_fp8w", xb, w8, wscale, ob, None, M, N, K, ldx, ldo, 3, 1)
-            return out
+    fp8 = isinstance(wp, tuple)     # (FP8 pack, per-row scales): ops.pack_weight_fp8 -- the opt-in FP8 weight stream of the rollout
+    w, wscale = wp if fp8 else (wp, None)
+    assert w.numel() == N * K
+    if fp8:
+        assert w.dtype == torch.uint8 and wscale.numel() == N and side is None
+    if swiglu:
+        out = out if out is not None else torch.empty(M, N // 2, dtype=BF16, device=xb.device)
+        (ob, ldy), bias, mode, ksplit = _xarg(out), None, 3, 1
+    else:
         if out is None:
-            out = torch.empty((ksplit, M, N) if ksplit > 1 else (M, N), dtype=F32 if ksplit > 1 else out_dtype, device=dev)
+            out = torch.empty((ksplit, M, N) if ksplit > 1 else (M, N), dtype=F32 if ksplit > 1 else out_dtype, device=xb.device)
         if out.dim() == 3:
             assert out.dtype == F32 and out.shape[0] == ksplit and out.is_contiguous() and bias is None
             mode, ldy = 2, N
         else:
             mode, ldy = (1 if out.dtype == F32 else 0), _ld(out)
-        hip.call("gemm_skinny_fp8w", xb, w8, wscale, out, bias, M, N, K, ldx, ldy, mode, ksplit)
-        return out
-    w = wp
-    assert wp.numel() == N * K
-    if swiglu:
-        if out is None:
-            out = torch.empty(M, N // 2, dtype=BF16, device=dev)
-        ob, ldo = _xarg(out)
-        hip.call("gemm_skinny_bf16", xb, w, ob, None, M, N, K, ldx, K, ldo, 3, 1, _side(side))
-        return out
-    if out is None:
-        out = torch.empty((ksplit, M, N) if ksplit > 1 else (M, N), dtype=F32 if ksplit > 1 else out_dtype, device=dev)
-    if out.dim() == 3:
-        assert out.dtype == F32 and out.shape[0] == ksplit and out.is_contiguous() and bias is None
-        mode, ldy = 2, N
+        ob, side = out, None        # side outputs exist for the fused-SwiGLU projection only
+    if fp8:
+        hip.call("gemm_skinny_fp8w", xb, w, wscale, ob, bias, M, N, K, ldx, ldy, mode, ksplit)
     else:
-        mode, ldy = (1 if out.dtype == F32 else 0), _ld(out)
-    hip.call("gemm_skinny_bf16", xb, w, out, bias, M, N, K, ldx, K, ldy, mode, ksplit, None)
+        hip.call("gemm_skinny_bf16", xb, w, ob, bias, M, N, K, ldx, K, ldy, mode, ksplit, _side(side))
     return out
 
 

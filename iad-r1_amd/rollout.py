@@ -84,7 +84,7 @@ class Rollout:
             ncu = self.decode_cus
         if H * Hq * D >= 1 << 20:
             self.ks_o = max(1, min(2, ncu // max(1, H // 16)))
-            # (the persistent split kernel takes <= 80 k-steps per slice -- the launcher's own gate, gemm.hip)
+            # (the persistent split kernel takes <= 80 k-steps per slice -- the launcher's own gate, skinny.hip)
             self.ks_down = 8 if (I // 32 + 7) // 8 <= 80 else max(1, min(8, ncu // max(1, H // 64)))
         else:
             self.ks_o, self.ks_down = 1, 1

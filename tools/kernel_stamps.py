@@ -59,12 +59,12 @@ slot = (torch.arange(M, device=dev, dtype=torch.int64) * 26 + 20) * 32 + 5
 cos = torch.ones(M, D // 2, device=dev); sin = torch.zeros(M, D // 2, device=dev)
 q_out = torch.empty(M, (Hq + 2 * Hkv) * D, dtype=torch.bfloat16, device=dev)
 us = timeit(lambda i: ops.gemm_qkv_rope_kv(x, pk[i % NL][0], pk[i % NL][1], q_out, cos, sin, slot, kc, vc, Hq, Hkv, D), NL)
-report("qkv+rope+kv (gemm_skinny_kernel<1,16>, 10.5 MB)", "gemm", [0, 1, 2, 3], 160, ["entry -> MFMAs done (loads + MFMA)", "LDS exchange + barrier", "epilogue (reduce, rope, stores)"], us)
+report("qkv+rope+kv (gemm_skinny_kernel<1,16>, 10.5 MB)", "skinny", [0, 1, 2, 3], 160, ["entry -> MFMAs done (loads + MFMA)", "LDS exchange + barrier", "epilogue (reduce, rope, stores)"], us)
 # ---- o projection (narrow kernel, split-K 2) ----------------------------------------------------------------------------------------------------
 ow = [ops.pack_weight(torch.randn(H, Hq * D, device=dev).to(torch.bfloat16) * 0.02) for _ in range(NL)]
 part = torch.empty(2, M, H, dtype=torch.float32, device=dev)
 us = timeit(lambda i: ops.gemm_skinny(x, ow[i % NL], H, out=part, ksplit=2), NL)
-report("o projection (gemm_skinny_kernel<1,16>, ksplit 2, 8.4 MB)", "gemm", [0, 1, 2], 256, ["entry -> MFMAs done (loads + MFMA)", "LDS exchange + barrier"], us)
+report("o projection (gemm_skinny_kernel<1,16>, ksplit 2, 8.4 MB)", "skinny", [0, 1, 2], 256, ["entry -> MFMAs done (loads + MFMA)", "LDS exchange + barrier"], us)
 # ---- row RMSNorm summing 8 slabs ----------------------------------------------------------------------------------------------------------------
 p8 = torch.randn(8, M, H, device=dev); res = torch.randn(M, H, device=dev).to(torch.bfloat16); w = torch.ones(H, device=dev, dtype=torch.bfloat16)
 y = ops.PackedAct(M, H, dev)
@@ -87,4 +87,4 @@ report("attn_decode (ctx 640, 42 MB of K/V)", "attn", [0, 1, 2, 3], 128, ["entry
 gu = [ops.pack_gateup(torch.randn(2 * I, H, device=dev).to(torch.bfloat16)) for _ in range(NL)]
 a = ops.PackedAct(M, I, dev)
 us = timeit(lambda i: ops.gemm_skinny(x, gu[i % NL], 2 * I, swiglu=True, out=a), NL)
-report("gate|up + SwiGLU (gemm_skinny_pers_kernel<8,8>, 90 MB)", "gemm", [4, 5, 6], 256, ["entry -> first group's MFMAs done", "remaining groups + epilogues"], us)
+report("gate|up + SwiGLU (gemm_skinny_pers_kernel<8,8>, 90 MB)", "skinny", [4, 5, 6], 256, ["entry -> first group's MFMAs done", "remaining groups + epilogues"], us)

@@ -12,20 +12,20 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libiadr1_hip.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wno-unused-result"]
-# per-file additions.  attn.hip: MFMA results in ordinary VGPRs -- the softmax / dS arithmetic works on the accumulators, and with them in AGPRs
+# per-file additions.  attn.hip, attn_decode.hip: MFMA results in ordinary VGPRs -- the softmax / dS arithmetic works on the accumulators, and with them in AGPRs
 # every such operation is a v_accvgpr_read + op + v_accvgpr_write (2-3 moves per MFMA in these kernels); none of them needs more than 256 registers
-EXTRA_FLAGS = {"attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+EXTRA_FLAGS = {f: ["-mllvm", "-amdgpu-mfma-vgpr-form=1"] for f in ("attn.hip", "attn_decode.hip")}
 if os.environ.get("IADR1_NO_EXTRA_FLAGS"):
     EXTRA_FLAGS = {}
 
 
-def sources():
-    return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
+def sources(ext=".hip"):
+    return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(ext))
 
 
 def _digest():
     h = hashlib.sha256()
-    for f in sources() + [os.path.join(CSRC, "common.h")]:
+    for f in sources() + sources(".h"):
         h.update(open(f, "rb").read())
     h.update(" ".join(FLAGS).encode())
     h.update(repr(sorted(EXTRA_FLAGS.items())).encode())

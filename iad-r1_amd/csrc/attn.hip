@@ -16,8 +16,7 @@
 //                                 accumulator registers of a lane are 8 CONSECUTIVE keys = one B fragment.
 // Backward = the same trick twice: bwd_dq owns q columns (dQ^T += K^T . dS^T), bwd_dkdv owns key
 // columns (dV^T += dO^T . P, dK^T += Q^T . dS) and loops the GQA group so dK/dV need no atomics.
-#include "common.h"
-#include <stdlib.h>
+#include "attn_common.h"
 
 namespace {
 
@@ -64,6 +63,8 @@ struct Cfg {
     static constexpr int DT = D / 16;               // 16-wide output tiles over d
     static constexpr int LD = 128;                  // 256-byte tile rows = exactly one LDS bank row, 16 chunks of 16 B (swizzled, see tile_off)
 };
+// dynamic LDS of the three tiled kernels (every D): two staged tiles of 64 / 32 / 32 rows, and the lse / delta rows of a q block for dK/dV
+constexpr int FWD_LDS = 2 * 64 * 256, DQ_LDS = 2 * 32 * 256, DKDV_LDS = 2 * 32 * 256 + 2 * 32 * 4;
 
 // LDS image of a staged [rows][d] tile.  Row r is 256 bytes; its 16-byte chunk c sits at chunk position  c ^ 2*rho(r),  rho(r) = (r & 3) | ((r >> 1) & 4).
 // Both read patterns of these kernels are then bank-conflict free (measured before, on 272-byte padded rows: SQ_LDS_BANK_CONFLICT = 39-43 % of
@@ -75,42 +76,16 @@ struct Cfg {
 //    in bits {0, 1, 3}, exactly the bits of rho, so the eight rows use eight different chunk pairs = all 64 banks once.
 // (the padded 272-byte-row form this replaced -- conflicts 0.40 -> 0.00, 1-5 % on the kernels -- is in profiles/EXPERIMENTS.md rounds 1-2; its compile-time switch was removed in round 6)
 __device__ __forceinline__ int swz_rho(int r) { return (r & 3) | ((r >> 1) & 4); }
-__device__ __forceinline__ int tile_off(int r, int c, int /*LD*/) { return r * 256 + ((c ^ (2 * swz_rho(r))) << 4); }    // byte offset of chunk c of row r
+__device__ __forceinline__ int tile_off(int r, int c) { return r * 256 + ((c ^ (2 * swz_rho(r))) << 4); }    // byte offset of chunk c of row r
 
-__device__ __forceinline__ bf16x8_t ld_frag_g(const bf16_t* p, bool ok) {
-    u32x4_t v = {0, 0, 0, 0};
-    if (ok) v = *(const u32x4_t*)p;
-    return __builtin_bit_cast(bf16x8_t, v);
-}
-__device__ __forceinline__ bf16x8_t ld_frag_s(const bf16_t* p) { return *(const bf16x8_t*)p; }
 // fragment (row, 16-byte chunk) of a staged tile
-template <int LD>
-__device__ __forceinline__ bf16x8_t ld_frag_t(const bf16_t* tile, int row, int chunk) { return *(const bf16x8_t*)((const char*)tile + tile_off(row, chunk, LD)); }
-
-// v_exp_f32 directly: exp2f() wraps it in a denormal-range rescale (~5 extra VALU instructions per call); softmax terms that small are zero anyway
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-__device__ __forceinline__ bf16x8_t pack_frag(const f32x4_t a, const f32x4_t b) {
-    u32x4_t v = {pack2bf(a[0], a[1]), pack2bf(a[2], a[3]), pack2bf(b[0], b[1]), pack2bf(b[2], b[3])};
-    return __builtin_bit_cast(bf16x8_t, v);
-}
+__device__ __forceinline__ bf16x8_t ld_frag_t(const bf16_t* tile, int row, int chunk) { return *(const bf16x8_t*)((const char*)tile + tile_off(row, chunk)); }
 
 // key (or q) row that MFMA-tile row i of 16-row tile `t` stands for, inside a 64/32-row block
 __device__ __forceinline__ int perm_row(int t, int i) { return (t >> 1) * 32 + (i >> 2) * 8 + (i & 3) + 4 * (t & 1); }
 
-// Stage `rows` token rows x D columns (global, row stride ld) into LDS row-major [rows][LD], zero filling
-// rows >= nvalid and columns >= D.
-template <int D, int ROWS>
-__device__ __forceinline__ void stage_rows(bf16_t* dst, const bf16_t* src, long long ld, int nvalid) {
-    constexpr int CPR = Cfg<D>::DQK / 8;
-    for (int idx = threadIdx.x; idx < ROWS * CPR; idx += 256) {
-        const int r = idx / CPR, c = idx - r * CPR;
-        u32x4_t v = {0, 0, 0, 0};
-        if (r < nvalid && c * 8 < D) v = *(const u32x4_t*)(src + (long long)r * ld + c * 8);
-        *(u32x4_t*)((char*)dst + tile_off(r, c, Cfg<D>::LD)) = v;
-    }
-}
-// Split staging (issue-early / write-late): the global loads of the NEXT tile are issued into registers before the
+// Tile staging, zero filling rows >= nvalid and columns >= D.
+// Split (issue-early / write-late): the global loads of the NEXT tile are issued into registers before the
 // MFMAs of the current tile and written to LDS after the barrier that ends it, so their latency hides under compute.
 template <int D, int ROWS, int NT = 256>
 struct TileRegs {
@@ -143,29 +118,10 @@ struct TileRegs {
         for (int i = 0; i < N; ++i) {
             const int idx = i * NT + threadIdx.x;
             const int r = idx / CPR, c = idx - r * CPR;
-            if (idx < ROWS * CPR) *(u32x4_t*)((char*)dst + tile_off(r, c, Cfg<D>::LD)) = v[i];
+            if (idx < ROWS * CPR) *(u32x4_t*)((char*)dst + tile_off(r, c)) = v[i];
         }
     }
 };
-
-// Same tile stored TRANSPOSED: dst[d][r], row stride LDT (elements), d in [0, DQK)
-template <int D, int ROWS, int LDT>
-__device__ __forceinline__ void stage_rows_t(bf16_t* dst, const bf16_t* src, long long ld, int nvalid) {
-    constexpr int CPR = Cfg<D>::DQK / 8;
-    for (int idx = threadIdx.x; idx < ROWS * CPR; idx += 256) {
-        // lanes walk rows fastest inside groups of 16 so that a wave's LDS writes hit 16 consecutive columns
-        const int r = (idx & 15) + (idx / (16 * CPR)) * 16, c = (idx >> 4) % CPR;
-        u32x4_t v = {0, 0, 0, 0};
-        if (r < nvalid && c * 8 < D) v = *(const u32x4_t*)(src + (long long)r * ld + c * 8);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            dst[(c * 8 + 2 * e) * LDT + r] = (bf16_t)(v[e] & 0xffffu);
-            dst[(c * 8 + 2 * e + 1) * LDT + r] = (bf16_t)(v[e] >> 16);
-        }
-    }
-}
-
-constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
 
 // hardware transpose reads: tr_frag_ld (common.h)
 // lane-constant part of a tr-read address inside a row-major [rows][LD] tile: row (li>>2) + 8*g, column 4*(li&3)
@@ -185,6 +141,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     bf16_t* Ks = (bf16_t*)smem;          // [BN][LD]
     bf16_t* Vs = Ks + BN * C::LD;        // [BN][LD] row-major; consumed through transpose reads
+    static_assert(FWD_LDS == 2 * BN * C::LD * 2, "launchers pass FWD_LDS");
 
     const int seg = blockIdx.y + p.seg_off, head = blockIdx.z, kvh = head / (p.Hq / p.Hkv);
     const int s0 = p.seg_start[seg], slen = p.seg_end[seg] - s0;
@@ -259,7 +216,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs p) {
         for (int ks = 0; ks < C::KS; ++ks) {
             bf16x8_t kf[4];
 #pragma unroll
-            for (int kt = 0; kt < 4; ++kt) kf[kt] = ld_frag_t<C::LD>(Ks, perm_row(kt, li), ks * 4 + g);
+            for (int kt = 0; kt < 4; ++kt) kf[kt] = ld_frag_t(Ks, perm_row(kt, li), ks * 4 + g);
 #pragma unroll
             for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
@@ -385,6 +342,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     bf16_t* Ks = (bf16_t*)smem;       // [KB][LD]  (also read transposed for dQ^T += K^T . dS^T)
     bf16_t* Vs = Ks + KB * C::LD;     // [KB][LD]
+    static_assert(DQ_LDS == 2 * KB * C::LD * 2, "launchers pass DQ_LDS");
 
     const int seg = blockIdx.y + p.seg_off, head = blockIdx.z, kvh = head / (p.Hq / p.Hkv);
     const int s0 = p.seg_start[seg], slen = p.seg_end[seg] - s0;
@@ -455,7 +413,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs p) {
 #pragma unroll
             for (int kt = 0; kt < 2; ++kt) {
                 const int row = perm_row(kt, li);
-                const bf16x8_t kfr = ld_frag_t<C::LD>(Ks, row, ks * 4 + g), vfr = ld_frag_t<C::LD>(Vs, row, ks * 4 + g);
+                const bf16x8_t kfr = ld_frag_t(Ks, row, ks * 4 + g), vfr = ld_frag_t(Vs, row, ks * 4 + g);
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
                     st[r][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfr, qf[r][ks], st[r][kt], 0, 0, 0);
@@ -517,6 +475,7 @@ __global__ __launch_bounds__(WAVES * 64) void attn_bwd_dkdv_kernel(AttnArgs p) {
     bf16_t* dOs = Qs + QB * C::LD;     // [QB][LD]  (also read transposed: dV^T += dO^T . P)
     float* lse_s = (float*)(dOs + QB * C::LD);    // [QB]
     float* del_s = lse_s + QB;                    // [QB]
+    static_assert(DKDV_LDS == 2 * QB * C::LD * 2 + 2 * QB * 4, "launchers pass DKDV_LDS");
 
     // grid = (key tile, kv head x head split, segment): the segment is the SLOWEST dimension of the dispatch order.  Shared-prefix segments (the prompts,
     // first in the segment list) carry ~15x the iterations of a completion segment (their query loop runs over all G children); dispatched in
@@ -614,8 +573,8 @@ __global__ __launch_bounds__(WAVES * 64) void attn_bwd_dkdv_kernel(AttnArgs p) {
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 const int row = perm_row(t, li);
-                s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ld_frag_t<C::LD>(Qs, row, ks * 4 + g), kf[ks], s[t], 0, 0, 0);
-                dp[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ld_frag_t<C::LD>(dOs, row, ks * 4 + g), vf[ks], dp[t], 0, 0, 0);
+                s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ld_frag_t(Qs, row, ks * 4 + g), kf[ks], s[t], 0, 0, 0);
+                dp[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ld_frag_t(dOs, row, ks * 4 + g), vf[ks], dp[t], 0, 0, 0);
             }
 #ifdef IADR1_STAMPS
         asm volatile("" :: "v"(s[0][0]), "v"(dp[1][3]));
@@ -740,483 +699,33 @@ __global__ __launch_bounds__(256) void attn_dkdv_reduce_kernel(AttnArgs p) {
     }
 }
 
-// =====================================================================================================
-// Paged-KV decode attention (rollout).  One query token per sequence.
-//   K cache page: [Hkv][PAGE=32][D] row-major;  V cache page: [Hkv][D][PAGE] (keys contiguous) so that both
-//   MFMA A operands are 16-byte contiguous global loads; a page is exactly one 32-key MFMA k-step.
-//   Block = (sequence, kv head); the `group` q heads of that kv head are the MFMA N dimension (<=16).
-//   4 waves take pages round-robin, each keeps an online-softmax state; combined through LDS at the end.
-//   Sequences of one GRPO group share their prompt pages through the block table (prefill once per prompt).
-// =====================================================================================================
-// K pages are stored in the MFMA A-fragment order attn_decode reads them in: kpk_off (common.h)
-
-struct DecodeArgs {
-    const bf16_t* q;          // [B, Hq*D] (row stride ldq)
-    const bf16_t* kcache;     // [npages][Hkv][32 x D in kpk_off order]
-    const bf16_t* vcache;     // [npages][Hkv][D][32]
-    const int* block_table;   // [B][max_pages]
-    const int* ctx_len;       // [B] number of valid keys (including the current token)
-    bf16_t* o;                // [B, Hq*D]
-    long long ldq, ldo;
-    int B, Hq, Hkv, max_pages;
-    float scale;
-    int gseq;                 // > 1: sequences [g * gseq, (g + 1) * gseq) share their prompt pages (group rollout) -> XCD-aware block order, see the kernel
-};
-
-template <int D, int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void attn_decode_kernel(DecodeArgs p, SideOut so) {
-    constexpr int KS = D / 32, DT = D / 16, PAGE = 32;
-    extern __shared__ float dsm[];
-    const int GS = (p.Hq / p.Hkv <= 8) ? 9 : 17;      // q-head columns kept per d (+1 pad): only `group` of the 16 MFMA columns are real
-    float* red_m = dsm;                                // [WAVES][16]
-    float* red_l = dsm + WAVES * 16;                   // [WAVES][16]
-    float* red_o = dsm + 2 * WAVES * 16;               // [WAVES][D][GS]
-    // Block -> (sequence, kv head).  Plain: grid (B, Hkv).  Group rollout (gseq > 1, 1-D grid): workgroup ids go round-robin over the 8 XCDs, each with its own
-    // L2, so the plain order scatters the gseq sequences that share a prompt's K/V pages over all XCDs and every copy is an L2 miss.  Here XCD x takes the prompt
-    // groups x, x + 8, ... and ALL blocks of a group (its sequences x kv heads) run on that one XCD: the pages come from HBM once and from L2 gseq - 1 times.
-    int b = blockIdx.x, kvh = blockIdx.y;
-    if (p.gseq > 1) {
-        const int id = blockIdx.x, npg = p.gseq * p.Hkv, k = id >> 3;
-        const int gi = (id & 7) + 8 * (k / npg), mem = k - (k / npg) * npg;
-        if (gi * p.gseq >= p.B) return;
-        kvh = mem / p.gseq;
-        b = gi * p.gseq + (mem - kvh * p.gseq);
-    }
-    const int group = p.Hq / p.Hkv;
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63, li = l & 15, g = l >> 4;
-    const long long sb = side_base(so);
-    STAMP(0);
-    const int n = p.ctx_len[b];
-    const int npage = (n + PAGE - 1) / PAGE;
-
-    bf16x8_t qf[KS];
-    {
-        const bool ok = li < group;
-        const bf16_t* src = p.q + (long long)b * p.ldq + (kvh * group + li) * D;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) qf[ks] = ld_frag_g(src + ks * 32 + g * 8, ok);
-    }
-    float m = -INFINITY, lsum = 0.f;
-    f32x4_t acc[DT];
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) acc[dt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-    const float c = p.scale * LOG2E;
-
-    for (int pg = w; pg < npage; pg += WAVES) {
-        const int phys = p.block_table[(long long)b * p.max_pages + pg];
-        const bf16_t* kp = p.kcache + ((long long)phys * p.Hkv + kvh) * PAGE * D;
-        const bf16_t* vp = p.vcache + ((long long)phys * p.Hkv + kvh) * D * PAGE;
-        // all K and V fragments of the page are requested up front: one memory latency per page, not two
-        bf16x8_t kfr[KS][2], vfr[DT];
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-            for (int t = 0; t < 2; ++t) kfr[ks][t] = ld_frag_g(kp + ((ks * 2 + t) * 64 + l) * 8, true);  // keys perm_row(li) + 4t (kpk_off)
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) vfr[dt] = ld_frag_g(vp + (dt * 16 + li) * PAGE + g * 8, true);
-        f32x4_t s[2] = {(f32x4_t){0.f, 0.f, 0.f, 0.f}, (f32x4_t){0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-            for (int t = 0; t < 2; ++t) s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfr[ks][t], qf[ks], s[t], 0, 0, 0);
-        float mx = -INFINITY;
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int key = pg * PAGE + g * 8 + t * 4 + e;
-                const float tv = key < n ? s[t][e] * c : -INFINITY;
-                s[t][e] = tv;
-                mx = fmaxf(mx, tv);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, WAVE));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, WAVE));
-        const float mn = fmaxf(m, mx);
-        const float alpha = (mn == -INFINITY) ? 1.f : fast_exp2(m - mn);
-        const float mref = (mn == -INFINITY) ? 0.f : mn;
-        float ps = 0.f;
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float pv = fast_exp2(s[t][e] - mref);
-                s[t][e] = pv;
-                ps += pv;
-            }
-        lsum = lsum * alpha + ps;
-        m = mn;
-        const bf16x8_t pf = pack_frag(s[0], s[1]);
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-            acc[dt] *= alpha;
-            acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfr[dt], pf, acc[dt], 0, 0, 0);
-        }
-    }
-    STAMP(1);
-    lsum += __shfl_xor(lsum, 16, WAVE);
-    lsum += __shfl_xor(lsum, 32, WAVE);
-    if (g == 0) { red_m[w * 16 + li] = m; red_l[w * 16 + li] = lsum; }
-    if (li < GS - 1) {
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) red_o[(w * D + dt * 16 + g * 4 + e) * GS + li] = acc[dt][e];
-    }
-    __syncthreads();
-    STAMP(2);
-    // combine the 4 partial states: thread -> (q head j, d)
-    for (int idx = threadIdx.x; idx < group * D; idx += WAVES * 64) {
-        const int j = idx / D, d = idx - j * D;
-        float M = red_m[j];
-#pragma unroll
-        for (int ww = 1; ww < WAVES; ++ww) M = fmaxf(M, red_m[ww * 16 + j]);
-        float num = 0.f, den = 0.f;
-#pragma unroll
-        for (int ww = 0; ww < WAVES; ++ww) {
-            const float f = (red_m[ww * 16 + j] == -INFINITY) ? 0.f : fast_exp2(red_m[ww * 16 + j] - M);
-            num += f * red_o[(ww * D + d) * GS + j];
-            den += f * red_l[ww * 16 + j];
-        }
-        const bf16_t ov = f2bf(den > 0.f ? num / den : 0.f);
-        p.o[p.ldo ? (long long)b * p.ldo + (kvh * group + j) * D + d : xpk_off(b, (kvh * group + j) * D + d, p.Hq * D)] = ov;
-        if (sb >= 0) {      // the row the attention backward of the policy reads, and its log-sum-exp (natural log, as attn_fwd stores it)
-            const long long r = sb + (long long)b * so.seq_stride;
-            ((bf16_t*)so.p0)[r * so.ld0 + (kvh * group + j) * D + d] = ov;
-            if (d == 0) ((float*)so.p1)[(long long)(kvh * group + j) * so.ld1 + r] = den > 0.f ? (M + log2f(den)) * LN2 : -INFINITY;
-        }
-    }
-    STAMP(3);
-}
-
-// Group-shared form of the decode attention for LONG shared prompts (LLaVA families: 3000-4000 prompt tokens; MHA decoders): the G sequences of a prompt group
-// share their full prompt pages through the block table, so ONE block per (group, kv head) reads those pages once for all G * (Hq / Hkv) query rows (up to NT
-// MFMA column tiles of 16) instead of every (sequence, kv head) block reading its own copy -- G times less K/V traffic for the prompt part, which is nearly all
-// of it (15 GB of 29 GB per decode step at LLaVA-OneVision-7B shapes).  Phase 1: the 8 waves walk the shared pages; their partial softmax states are combined
-// through LDS into one state per query row.  Phase 2: wave s takes sequence s of the group: its private pages (prompt remainder + completion), then the merge
-// with the shared state of its rows and the output / side-output stores.  No cross-block exchange; grid = (groups, Hkv).
-struct DecodeGroupArgs {
-    DecodeArgs a;
-    const int* shared_pages;  // [B / G]: leading block-table entries (full prompt pages) shared by the G sequences of a group
-    int G;
-    // Few (group, kv head) pairs and very long prompts (LLaVA-OneVision-7B: 8 x 4 blocks for 3900 shared tokens): the shared pages are split over `chunks` blocks
-    // (grid.z) in a first launch (mode 1) that leaves one partial state per (group, kv head, chunk, row) in `ws`; a second launch (mode 2, grid (groups, Hkv))
-    // merges them and runs phase 2.  mode 0: both phases in one launch.
-    int mode, chunks;
-    float* ws;                // [groups][Hkv][chunks][RMAX][D + 2]: o[D], m, l per row
-};
-
-template <int D, int NT>
-__global__ __launch_bounds__(512) void attn_decode_group_kernel(DecodeGroupArgs gp, SideOut so) {
-    constexpr int KS = D / 32, DT = D / 16, PAGE = 32, WAVES = 8, RMAX = 16 * NT, GS = 17;
-    const DecodeArgs& p = gp.a;
-    extern __shared__ float dsm[];
-    float* red_m = dsm;                                 // [WAVES][16]
-    float* red_l = red_m + WAVES * 16;                  // [WAVES][16]
-    float* red_o = red_l + WAVES * 16;                  // [WAVES][D][GS]
-    float* sh_m = red_o + WAVES * D * GS;               // [RMAX] state of the shared part per query row (log2 domain, like m / l below)
-    float* sh_l = sh_m + RMAX;
-    float* sh_o = sh_l + RMAX;                          // [RMAX][D]
-    const int gi = blockIdx.x, kvh = blockIdx.y, group = p.Hq / p.Hkv, G = gp.G;
-    const int rows = G * group;                         // <= RMAX (host checks)
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63, li = l & 15, g = l >> 4;
-    const long long sb = side_base(so);
-    const int b0 = gi * G;
-    const int ns = gp.shared_pages[gi];
-    const float c = p.scale * LOG2E;
-
-    // ---- phase 1: shared pages, all query rows of the group ----------------------------------------------------------------------------------
-    // Q fragments of the NT column tiles live in LDS in fragment order (one conflict-free 16-byte read per fragment and page): 64 VGPRs less than keeping
-    // them in registers, which with the 128 accumulator registers of NT = 4 spilled to scratch
-    bf16_t* qs = (bf16_t*)(sh_o + RMAX * D);            // [NT][KS][64 lanes][8]
-    for (int t = w; t < NT; t += WAVES) {
-        const int r = t * 16 + li, sq = r / group, j = r - sq * group;
-        const bool ok = r < rows;
-        const bf16_t* src = p.q + (long long)(b0 + (ok ? sq : 0)) * p.ldq + (kvh * group + (ok ? j : 0)) * D;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) *(bf16x8_t*)(qs + ((t * KS + ks) * 64 + l) * 8) = ld_frag_g(src + ks * 32 + g * 8, ok);
-    }
-    __syncthreads();
-    float m[NT], lsum[NT];
-    f32x4_t acc[NT][DT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        m[t] = -INFINITY;
-        lsum[t] = 0.f;
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) acc[t][dt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-    }
-    const int per = gp.mode == 1 ? (ns + gp.chunks - 1) / gp.chunks : ns;           // pages of this block's chunk (mode 1: blockIdx.z)
-    const int pg0 = gp.mode == 1 ? (int)blockIdx.z * per : 0, pg1 = gp.mode == 2 ? 0 : min(ns, pg0 + per);
-    float* wsb = gp.ws + (((long long)gi * p.Hkv + kvh) * gp.chunks) * RMAX * (D + 2);
-    for (int pg = pg0 + w; pg < pg1; pg += WAVES) {
-        asm volatile("" ::: "memory");      // keeps the (loop-invariant) Q fragment reads inside the loop: hoisted, they are 64 registers again
-        const int phys = p.block_table[(long long)b0 * p.max_pages + pg];
-        const bf16_t* kp = p.kcache + ((long long)phys * p.Hkv + kvh) * PAGE * D;
-        const bf16_t* vp = p.vcache + ((long long)phys * p.Hkv + kvh) * D * PAGE;
-        bf16x8_t kfr[KS][2], vfr[DT];
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-            for (int t2 = 0; t2 < 2; ++t2) kfr[ks][t2] = ld_frag_g(kp + ((ks * 2 + t2) * 64 + l) * 8, true);
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) vfr[dt] = ld_frag_g(vp + (dt * 16 + li) * PAGE + g * 8, true);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {      // every key of a shared page is a prompt token of every sequence of the group: no masking
-            f32x4_t sc[2] = {(f32x4_t){0.f, 0.f, 0.f, 0.f}, (f32x4_t){0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-                for (int t2 = 0; t2 < 2; ++t2)
-                    sc[t2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfr[ks][t2], *(const bf16x8_t*)(qs + ((t * KS + ks) * 64 + l) * 8), sc[t2], 0, 0, 0);
-            float mx = -INFINITY;
-#pragma unroll
-            for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { sc[t2][e] *= c; mx = fmaxf(mx, sc[t2][e]); }
-            mx = fmaxf(mx, __shfl_xor(mx, 16, WAVE));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, WAVE));
-            const float mn = fmaxf(m[t], mx);
-            const float alpha = fast_exp2(m[t] - mn);           // m = -inf on the first page: exp2(-inf) = 0
-            float ps = 0.f;
-#pragma unroll
-            for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { sc[t2][e] = fast_exp2(sc[t2][e] - mn); ps += sc[t2][e]; }
-            lsum[t] = lsum[t] * alpha + ps;
-            m[t] = mn;
-            const bf16x8_t pf = pack_frag(sc[0], sc[1]);
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt) {
-                acc[t][dt] *= alpha;
-                acc[t][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfr[dt], pf, acc[t][dt], 0, 0, 0);
-            }
-        }
-    }
-    // combine the 8 waves' states, one column tile at a time, into the per-row shared state (LDS; mode 1: this chunk's slot of the workspace)
-#pragma unroll
-    for (int t = 0; t < NT && gp.mode != 2; ++t) {
-        float ls = lsum[t];
-        ls += __shfl_xor(ls, 16, WAVE);
-        ls += __shfl_xor(ls, 32, WAVE);
-        if (g == 0) { red_m[w * 16 + li] = m[t]; red_l[w * 16 + li] = ls; }
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) red_o[(w * D + dt * 16 + g * 4 + e) * GS + li] = acc[t][dt][e];
-        __syncthreads();
-        for (int idx = threadIdx.x; idx < 16 * D; idx += WAVES * 64) {
-            const int j = idx / D, d = idx - j * D;
-            float M = red_m[j];
-#pragma unroll
-            for (int ww = 1; ww < WAVES; ++ww) M = fmaxf(M, red_m[ww * 16 + j]);
-            float num = 0.f, den = 0.f;
-#pragma unroll
-            for (int ww = 0; ww < WAVES; ++ww) {
-                const float f = (red_m[ww * 16 + j] == -INFINITY) ? 0.f : fast_exp2(red_m[ww * 16 + j] - M);
-                num += f * red_o[(ww * D + d) * GS + j];
-                den += f * red_l[ww * 16 + j];
-            }
-            if (gp.mode == 1) {
-                float* dst = wsb + ((long long)blockIdx.z * RMAX + t * 16 + j) * (D + 2);
-                dst[d] = num;
-                if (d == 0) { dst[D] = M; dst[D + 1] = den; }
-            } else {
-                sh_o[(t * 16 + j) * D + d] = num;
-                if (d == 0) { sh_m[t * 16 + j] = M; sh_l[t * 16 + j] = den; }
-            }
-        }
-        __syncthreads();
-    }
-    if (gp.mode == 1) return;
-    if (gp.mode == 2) {      // merge the chunks' partial states of the first launch (fixed order: reproducible)
-        for (int idx = threadIdx.x; idx < rows * D; idx += WAVES * 64) {
-            const int r = idx / D, d = idx - r * D;
-            float M = -INFINITY;
-            for (int cc = 0; cc < gp.chunks; ++cc) M = fmaxf(M, wsb[((long long)cc * RMAX + r) * (D + 2) + D]);
-            float num = 0.f, den = 0.f;
-            for (int cc = 0; cc < gp.chunks; ++cc) {
-                const float* src = wsb + ((long long)cc * RMAX + r) * (D + 2);
-                const float f = (src[D] == -INFINITY) ? 0.f : fast_exp2(src[D] - M);
-                num += f * src[d];
-                den += f * src[D + 1];
-            }
-            sh_o[r * D + d] = num;
-            if (d == 0) { sh_m[r] = M; sh_l[r] = den; }
-        }
-        __syncthreads();
-    }
-
-    // ---- phase 2: wave s <- sequence s of the group: private pages, merge with the shared state, stores ----------------------------------------
-    for (int sq = w; sq < G; sq += WAVES) {
-        const int b = b0 + sq;
-        const int n = p.ctx_len[b];
-        const int npage = (n + PAGE - 1) / PAGE;
-        bf16x8_t q1[KS];
-        {
-            const bool ok = li < group;
-            const bf16_t* src = p.q + (long long)b * p.ldq + (kvh * group + (ok ? li : 0)) * D;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) q1[ks] = ld_frag_g(src + ks * 32 + g * 8, ok);
-        }
-        float m1 = -INFINITY, l1 = 0.f;
-        f32x4_t a1[DT];
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) a1[dt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-        for (int pg = ns; pg < npage; ++pg) {
-            const int phys = p.block_table[(long long)b * p.max_pages + pg];
-            const bf16_t* kp = p.kcache + ((long long)phys * p.Hkv + kvh) * PAGE * D;
-            const bf16_t* vp = p.vcache + ((long long)phys * p.Hkv + kvh) * D * PAGE;
-            bf16x8_t kfr[KS][2], vfr[DT];
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-                for (int t2 = 0; t2 < 2; ++t2) kfr[ks][t2] = ld_frag_g(kp + ((ks * 2 + t2) * 64 + l) * 8, true);
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt) vfr[dt] = ld_frag_g(vp + (dt * 16 + li) * PAGE + g * 8, true);
-            f32x4_t sc[2] = {(f32x4_t){0.f, 0.f, 0.f, 0.f}, (f32x4_t){0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-                for (int t2 = 0; t2 < 2; ++t2) sc[t2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfr[ks][t2], q1[ks], sc[t2], 0, 0, 0);
-            float mx = -INFINITY;
-#pragma unroll
-            for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int key = pg * PAGE + g * 8 + t2 * 4 + e;
-                    const float tv = key < n ? sc[t2][e] * c : -INFINITY;
-                    sc[t2][e] = tv;
-                    mx = fmaxf(mx, tv);
-                }
-            mx = fmaxf(mx, __shfl_xor(mx, 16, WAVE));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, WAVE));
-            const float mn = fmaxf(m1, mx);
-            const float alpha = (mn == -INFINITY) ? 1.f : fast_exp2(m1 - mn);
-            const float mref = (mn == -INFINITY) ? 0.f : mn;
-            float ps = 0.f;
-#pragma unroll
-            for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { sc[t2][e] = fast_exp2(sc[t2][e] - mref); ps += sc[t2][e]; }
-            l1 = l1 * alpha + ps;
-            m1 = mn;
-            const bf16x8_t pf = pack_frag(sc[0], sc[1]);
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt) {
-                a1[dt] *= alpha;
-                a1[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfr[dt], pf, a1[dt], 0, 0, 0);
-            }
-        }
-        l1 += __shfl_xor(l1, 16, WAVE);
-        l1 += __shfl_xor(l1, 32, WAVE);
-        if (li < group) {       // lane (li = head j of the group, g): dims dt * 16 + g * 4 + e
-            const int r = sq * group + li;
-            const float ms = sh_m[r], lsh = sh_l[r];
-            const float M = fmaxf(ms, m1);
-            const float fs = (ms == -INFINITY) ? 0.f : fast_exp2(ms - M), f1 = (m1 == -INFINITY) ? 0.f : fast_exp2(m1 - M);
-            const float den = fs * lsh + f1 * l1;
-            const float inv = den > 0.f ? 1.f / den : 0.f;
-            const int col0 = (kvh * group + li) * D;
-            const long long rr = sb >= 0 ? sb + (long long)b * so.seq_stride : 0;
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt) {
-                const int d = dt * 16 + g * 4;
-                const f32x4_t so4 = *(const f32x4_t*)(sh_o + (long long)r * D + d);
-                const u32x2_t ov = {pack2bf((fs * so4[0] + f1 * a1[dt][0]) * inv, (fs * so4[1] + f1 * a1[dt][1]) * inv),
-                                    pack2bf((fs * so4[2] + f1 * a1[dt][2]) * inv, (fs * so4[3] + f1 * a1[dt][3]) * inv)};
-                *(u32x2_t*)(p.o + (p.ldo ? (long long)b * p.ldo + col0 + d : xpk_off(b, col0 + d, p.Hq * D))) = ov;
-                if (sb >= 0) *(u32x2_t*)((bf16_t*)so.p0 + rr * so.ld0 + col0 + d) = ov;
-            }
-            if (sb >= 0 && g == 0) ((float*)so.p1)[(long long)(kvh * group + li) * so.ld1 + rr] = den > 0.f ? (M + log2f(den)) * LN2 : -INFINITY;
-        }
-    }
-}
-
-// Write K/V rows of `T` tokens into the paged cache (prefill: many tokens; decode: one per sequence).
-// slot[t] = physical page * 32 + offset, or < 0 to skip (padding).
-template <int D>
-__global__ __launch_bounds__(256) void kv_store_kernel(const bf16_t* k, long long ldk, const bf16_t* v, long long ldv, const long long* slot,
-                                                       bf16_t* kcache, bf16_t* vcache, int T, int Hkv) {
-    constexpr int CPR = D / 8;
-    const long long total = (long long)T * Hkv * CPR;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-        const int c = (int)(i % CPR);
-        const long long th = i / CPR;
-        const int h = (int)(th % Hkv);
-        const long long t = th / Hkv;
-        const long long sl = slot[t];
-        if (sl < 0) continue;
-        const long long page = sl >> 5;
-        const int off = (int)(sl & 31);
-        const u32x4_t kv = *(const u32x4_t*)(k + t * ldk + h * D + c * 8);
-        *(u32x4_t*)(kcache + (page * Hkv + h) * 32 * D + kpk_off(off, c * 8)) = kv;
-        const u32x4_t vv = *(const u32x4_t*)(v + t * ldv + h * D + c * 8);
-        bf16_t* vd = vcache + (page * Hkv + h) * (long long)D * 32 + off;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            vd[(c * 8 + 2 * e) * 32] = (bf16_t)(vv[e] & 0xffffu);
-            vd[(c * 8 + 2 * e + 1) * 32] = (bf16_t)(vv[e] >> 16);
-        }
-    }
-}
-
-// Decode-step fusion: rotary on the q and k heads of each new token (in place for q; k goes straight to its
-// cache row) + v into the transposed cache page.  One launch instead of rope + kv_store.
-template <int D>
-__global__ __launch_bounds__(256) void rope_kv_store_kernel(bf16_t* qkv, long long ld, const float* cs, const float* sn, const long long* slot,
-                                                            bf16_t* kcache, bf16_t* vcache, int T, int Hq, int Hkv) {
-    constexpr int HALF = D / 2, RC = HALF / 4, VC = D / 8;   // rope items (4-element pairs) and v items (8 elements) per head
-    const int per_tok = (Hq + Hkv) * RC + Hkv * VC;
-    const long long total = (long long)T * per_tok;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-        const long long t = i / per_tok;
-        int r = (int)(i - t * per_tok);
-        const long long sl = slot[t];
-        const long long page = sl >> 5;
-        const int off = (int)(sl & 31);
-        bf16_t* row = qkv + t * ld;
-        if (r < (Hq + Hkv) * RC) {
-            const int h = r / RC, c = r - h * RC;
-            bf16_t* p = row + h * D + c * 4;
-            const u32x2_t lo = *(const u32x2_t*)p, hi = *(const u32x2_t*)(p + HALF);
-            const f32x4_t cc = *(const f32x4_t*)(cs + t * HALF + c * 4), ss = *(const f32x4_t*)(sn + t * HALF + c * 4);
-            const float a[4] = {lo_bf(lo[0]), hi_bf(lo[0]), lo_bf(lo[1]), hi_bf(lo[1])};
-            const float b[4] = {lo_bf(hi[0]), hi_bf(hi[0]), lo_bf(hi[1]), hi_bf(hi[1])};
-            float oa[4], ob[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { oa[e] = a[e] * cc[e] - b[e] * ss[e]; ob[e] = b[e] * cc[e] + a[e] * ss[e]; }
-            const u32x2_t va = {pack2bf(oa[0], oa[1]), pack2bf(oa[2], oa[3])}, vb = {pack2bf(ob[0], ob[1]), pack2bf(ob[2], ob[3])};
-            if (h < Hq) {
-                *(u32x2_t*)p = va;
-                *(u32x2_t*)(p + HALF) = vb;
-            } else if (sl >= 0) {
-                bf16_t* kd = kcache + (page * Hkv + (h - Hq)) * 32 * D;
-                *(u32x2_t*)(kd + kpk_off(off, c * 4)) = va;
-                *(u32x2_t*)(kd + kpk_off(off, c * 4 + HALF)) = vb;
-            }
-        } else if (sl >= 0) {
-            r -= (Hq + Hkv) * RC;
-            const int h = r / VC, c = r - h * VC;
-            const u32x4_t vv = *(const u32x4_t*)(row + (Hq + Hkv + h) * D + c * 8);
-            bf16_t* vd = vcache + (page * Hkv + h) * (long long)D * 32 + off;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                vd[(c * 8 + 2 * e) * 32] = (bf16_t)(vv[e] & 0xffffu);
-                vd[(c * 8 + 2 * e + 1) * 32] = (bf16_t)(vv[e] >> 16);
-            }
-        }
-    }
-}
-
-template <typename K>
-void set_smem(K kern, int bytes) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); }
-
 }  // namespace
 
-static int check_common(int T, int Hq, int Hkv, int D, long long ldq, long long ldk, long long ldv, long long ldo) {
+// Launcher configuration, fixed at first use: every instantiation the entry points below can launch is opted in for its dynamic LDS
+static void attn_lds_optin() {
+    static const bool done = [] {
+        const struct { const void* kernel; int bytes; } list[] = {
+            {(const void*)attn_fwd_kernel<128, 1>, FWD_LDS},          {(const void*)attn_fwd_kernel<80, 1>, FWD_LDS},
+            {(const void*)attn_bwd_dq_kernel<128, 1>, DQ_LDS},        {(const void*)attn_bwd_dq_kernel<80, 1>, DQ_LDS},
+            {(const void*)attn_bwd_dq_kernel<128, 2>, DQ_LDS},        {(const void*)attn_bwd_dq_kernel<80, 2>, DQ_LDS},
+            {(const void*)attn_bwd_dkdv_kernel<128, 4>, DKDV_LDS},    {(const void*)attn_bwd_dkdv_kernel<80, 4>, DKDV_LDS},
+            {(const void*)attn_bwd_dkdv_kernel<128, 8>, DKDV_LDS},    {(const void*)attn_bwd_dkdv_kernel<80, 8>, DKDV_LDS},
+        };
+        for (const auto& e : list) (void)hipFuncSetAttribute(e.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e.bytes);
+        return true;
+    }();
+    (void)done;
+}
+
+// Checks and kernel arguments the three entry points share
+static int attn_args(AttnArgs* p, const void* q, const void* k, const void* v, float* lse, const int* seg_start, const int* seg_end, const int* seg_prefix, int T, int Hq, int Hkv, int D, long long ldq, long long ldk, long long ldv, long long ldo, int causal, float scale) {
     IADR1_REQUIRE(D == 128 || D == 80, "attention: head dim %d not built (128 and 80 are)", D);
     IADR1_REQUIRE(T > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0, "attention: bad head counts Hq=%d Hkv=%d", Hq, Hkv);
     IADR1_REQUIRE((ldq % 8) == 0 && (ldk % 8) == 0 && (ldv % 8) == 0 && (ldo % 8) == 0, "attention: row strides must be multiples of 8 elements");
+    p->q = (const bf16_t*)q; p->k = (const bf16_t*)k; p->v = (const bf16_t*)v; p->lse = lse;
+    p->seg_start = seg_start; p->seg_end = seg_end; p->seg_prefix = seg_prefix; p->ldq = ldq; p->ldk = ldk; p->ldv = ldv; p->ldo = ldo;
+    p->T = T; p->Hq = Hq; p->Hkv = Hkv; p->causal = causal; p->scale = scale;
+    attn_lds_optin();
     return IADR1_OK;
 }
 
@@ -1235,33 +744,25 @@ static int seg_ranges(int nseg, int max_seqlen, int nseg_head, int max_seqlen_ta
     return 1;
 }
 
+// 64-row q tiles (~180 VGPR, 2 blocks/CU) measured 1.4x faster than 128-row tiles (1 block/CU): occupancy wins (profiles/EXPERIMENTS.md rounds 1-2)
+template <int D>
+static void launch_fwd(const AttnArgs& p, int max_rows, int nseg, hipStream_t stream) {
+    hipLaunchKernelGGL((attn_fwd_kernel<D, 1>), dim3((max_rows + 63) / 64, nseg, p.Hq), dim3(256), FWD_LDS, stream, p);
+}
+
 extern "C" int iadr1_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const int* seg_start, const int* seg_end,
                               const int* seg_prefix, int nseg, int max_seqlen, int nseg_head, int max_seqlen_tail, int T, int Hq, int Hkv, int D, long long ldq, long long ldk, long long ldv,
                               long long ldo, int causal, float scale, hipStream_t stream) {
-    if (int e = check_common(T, Hq, Hkv, D, ldq, ldk, ldv, ldo)) return e;
-    IADR1_REQUIRE(nseg > 0 && max_seqlen > 0, "attn_fwd: empty segment list");
     AttnArgs p{};
-    p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.o = (bf16_t*)o; p.lse = lse;
-    p.seg_start = seg_start; p.seg_end = seg_end; p.seg_prefix = seg_prefix; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
-    p.T = T; p.Hq = Hq; p.Hkv = Hkv; p.causal = causal; p.scale = scale;
-    constexpr int force_r = 1;      // query tiles per block (2 measured slower: profiles/EXPERIMENTS.md rounds 1-2)
+    if (int e = attn_args(&p, q, k, v, lse, seg_start, seg_end, seg_prefix, T, Hq, Hkv, D, ldq, ldk, ldv, ldo, causal, scale)) return e;
+    IADR1_REQUIRE(nseg > 0 && max_seqlen > 0, "attn_fwd: empty segment list");
+    p.o = (bf16_t*)o;
     SegRange rg[2];
     const int nr = seg_ranges(nseg, max_seqlen, nseg_head, max_seqlen_tail, rg);
     for (int ri = 0; ri < nr; ++ri) {
         p.seg_off = rg[ri].off;
-        const int ml = rg[ri].maxlen, ns = rg[ri].n;
-        // 64-row q tiles (R=1, ~180 VGPR, 2 blocks/CU) measured 1.4x faster than 128-row tiles (R=2, 1 block/CU): occupancy wins
-        const bool small = ml <= 64 || force_r == 1;
-#define LAUNCH_FWD(DD, RR)                                                                                           \
-    do {                                                                                                             \
-        const int smem = (2 * 64 * Cfg<DD>::LD) * 2;                                                                 \
-        set_smem(attn_fwd_kernel<DD, RR>, smem);                                                                     \
-        const int bm = 64 * RR;                                                                                      \
-        hipLaunchKernelGGL((attn_fwd_kernel<DD, RR>), dim3((ml + bm - 1) / bm, ns, Hq), dim3(256), smem, stream, p); \
-    } while (0)
-        if (D == 128) { if (small) LAUNCH_FWD(128, 1); else LAUNCH_FWD(128, 2); }
-        else { if (small) LAUNCH_FWD(80, 1); else LAUNCH_FWD(80, 2); }
-#undef LAUNCH_FWD
+        if (D == 128) launch_fwd<128>(p, rg[ri].maxlen, rg[ri].n, stream);
+        else launch_fwd<80>(p, rg[ri].maxlen, rg[ri].n, stream);
     }
     return iadr1_check_launch("attn_fwd");
 }
@@ -1270,21 +771,36 @@ extern "C" int iadr1_attn_fwd(const void* q, const void* k, const void* v, void*
 extern "C" int iadr1_attn_fwd_chunk(const void* q, const void* k, const void* v, void* o, float* lse, const int* seg_start, const int* seg_end,
                                     const int* seg_prefix, const int* seg_view, int nseg, int max_q_count, int T, int Hq, int Hkv, int D, long long ldq,
                                     long long ldk, long long ldv, long long ldo, float scale, hipStream_t stream) {
-    if (int e = check_common(T, Hq, Hkv, D, ldq, ldk, ldv, ldo)) return e;
-    IADR1_REQUIRE(nseg > 0 && max_q_count > 0 && seg_view != nullptr, "attn_fwd_chunk: empty segment list / no segment views");
     AttnArgs p{};
-    p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.o = (bf16_t*)o; p.lse = lse;
-    p.seg_start = seg_start; p.seg_end = seg_end; p.seg_prefix = seg_prefix; p.seg_view = seg_view; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
-    p.T = T; p.Hq = Hq; p.Hkv = Hkv; p.causal = 1; p.scale = scale;
-    const int smem = (2 * 64 * Cfg<128>::LD) * 2;
-    if (D == 128) {
-        set_smem(attn_fwd_kernel<128, 1>, smem);
-        hipLaunchKernelGGL((attn_fwd_kernel<128, 1>), dim3((max_q_count + 63) / 64, nseg, Hq), dim3(256), smem, stream, p);
-    } else {
-        set_smem(attn_fwd_kernel<80, 1>, smem);
-        hipLaunchKernelGGL((attn_fwd_kernel<80, 1>), dim3((max_q_count + 63) / 64, nseg, Hq), dim3(256), smem, stream, p);
-    }
+    if (int e = attn_args(&p, q, k, v, lse, seg_start, seg_end, seg_prefix, T, Hq, Hkv, D, ldq, ldk, ldv, ldo, 1, scale)) return e;
+    IADR1_REQUIRE(nseg > 0 && max_q_count > 0 && seg_view != nullptr, "attn_fwd_chunk: empty segment list / no segment views");
+    p.o = (bf16_t*)o; p.seg_view = seg_view;
+    if (D == 128) launch_fwd<128>(p, max_q_count, nseg, stream);
+    else launch_fwd<80>(p, max_q_count, nseg, stream);
     return iadr1_check_launch("attn_fwd_chunk");
+}
+
+// delta, then per launch range dQ, dK/dV and (head split) the reduction of its partials.  Segments of at most 64 rows take the small forms; the large ones
+// (8-wave dK/dV, two query tiles per dQ block) are the measured choices for the rest (profiles/EXPERIMENTS.md rounds 1-2)
+template <int D>
+static void launch_bwd(AttnArgs& p, const void* o, float* delta, const SegRange* rg, int nr, int hs_all, hipStream_t stream) {
+    const long long items = (long long)p.T * p.Hq * 16;
+    hipLaunchKernelGGL(attn_delta_kernel<D>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, stream, (const bf16_t*)o, p.ldo, p.dout, p.lddo, delta, p.T, p.Hq);
+    for (int ri = 0; ri < nr; ++ri) {
+        p.seg_off = rg[ri].off;
+        const int ml = rg[ri].maxlen, ns = rg[ri].n;
+        // the head split of dK/dV balances the long query loops of shared-prefix segments: only the head range needs it (a short
+        // segment split 4 ways is 4x the blocks for 9 iterations each)
+        p.hs = (nr == 2 && ri == 1) ? 1 : hs_all;
+        if (ml > 64) {
+            hipLaunchKernelGGL((attn_bwd_dq_kernel<D, 2>), dim3((ml + 127) / 128, ns, p.Hq), dim3(256), DQ_LDS, stream, p);
+            hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, 8>), dim3((ml + 127) / 128, p.Hkv * p.hs, ns), dim3(512), DKDV_LDS, stream, p);
+        } else {
+            hipLaunchKernelGGL((attn_bwd_dq_kernel<D, 1>), dim3((ml + 63) / 64, ns, p.Hq), dim3(256), DQ_LDS, stream, p);
+            hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, 4>), dim3((ml + 63) / 64, p.Hkv * p.hs, ns), dim3(256), DKDV_LDS, stream, p);
+        }
+        if (p.hs > 1) hipLaunchKernelGGL(attn_dkdv_reduce_kernel<D>, dim3((ml * p.Hkv * 2 * (D / 4) + 255) / 256, ns), dim3(256), 0, stream, p);
+    }
 }
 
 extern "C" int iadr1_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, float* delta,
@@ -1292,145 +808,31 @@ extern "C" int iadr1_attn_bwd(const void* q, const void* k, const void* v, const
                               int nseg_head, int max_seqlen_tail, int T,
                               int Hq, int Hkv, int D, long long ldq, long long ldk, long long ldv, long long ldo, long long lddo,
                               long long lddq, long long lddk, long long lddv, int causal, float scale, hipStream_t stream) {
-    if (int e = check_common(T, Hq, Hkv, D, ldq, ldk, ldv, ldo)) return e;
+    AttnArgs p{};
+    if (int e = attn_args(&p, q, k, v, (float*)lse, seg_start, seg_end, seg_prefix, T, Hq, Hkv, D, ldq, ldk, ldv, ldo, causal, scale)) return e;
     IADR1_REQUIRE((lddo % 8) == 0 && (lddq % 8) == 0 && (lddk % 8) == 0 && (lddv % 8) == 0, "attn_bwd: gradient row strides must be multiples of 8");
     IADR1_REQUIRE(nseg > 0 && max_seqlen > 0, "attn_bwd: empty segment list");
-    AttnArgs p{};
-    p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.lse = (float*)lse;
-    p.seg_start = seg_start; p.seg_end = seg_end; p.seg_prefix = seg_prefix; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
-    p.T = T; p.Hq = Hq; p.Hkv = Hkv; p.causal = causal; p.scale = scale;
     p.dout = (const bf16_t*)dout; p.delta = delta; p.dq = (bf16_t*)dq; p.dk = (bf16_t*)dk; p.dv = (bf16_t*)dv;
     p.lddo = lddo; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
     const int hs_all = (dkv_ws && head_splits > 1) ? head_splits : 1;
     IADR1_REQUIRE((Hq / Hkv) % hs_all == 0, "attn_bwd: head_splits=%d must divide the GQA group %d", hs_all, Hq / Hkv);
     p.dkv_ws = dkv_ws;
-    const long long items = (long long)T * Hq * 16;
-    constexpr int dq_r = 2, kv_waves = 8;      // the measured choices (8-wave dK/dV, two query tiles per dQ block: profiles/EXPERIMENTS.md rounds 1-2)
     SegRange rg[2];
     const int nr = seg_ranges(nseg, max_seqlen, nseg_head, max_seqlen_tail, rg);
-#define LAUNCH_BWD(DD)                                                                                                                   \
-    do {                                                                                                                                 \
-        hipLaunchKernelGGL(attn_delta_kernel<DD>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, stream, (const bf16_t*)o, ldo,    \
-                           (const bf16_t*)dout, lddo, delta, T, Hq);                                                                     \
-        for (int ri = 0; ri < nr; ++ri) {                                                                                                \
-            p.seg_off = rg[ri].off;                                                                                                      \
-            const int ml = rg[ri].maxlen, ns = rg[ri].n;                                                                                 \
-            /* the head split of dK/dV balances the long query loops of shared-prefix segments: only the head range needs it (a short  */ \
-            /* segment split 4 ways is 4x the blocks for 9 iterations each)                                                            */ \
-            p.hs = (nr == 2 && ri == 1) ? 1 : hs_all;                                                                                    \
-            const int smem_dq = (2 * 32 * Cfg<DD>::LD) * 2;                                                                              \
-            if (dq_r == 2 && ml > 64) {                                                                                                  \
-                set_smem(attn_bwd_dq_kernel<DD, 2>, smem_dq);                                                                            \
-                hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, 2>), dim3((ml + 127) / 128, ns, Hq), dim3(256), smem_dq, stream, p);          \
-            } else {                                                                                                                     \
-                set_smem(attn_bwd_dq_kernel<DD, 1>, smem_dq);                                                                            \
-                hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, 1>), dim3((ml + 63) / 64, ns, Hq), dim3(256), smem_dq, stream, p);            \
-            }                                                                                                                            \
-            const int smem_kv = (2 * 32 * Cfg<DD>::LD) * 2 + 64 * 4;                                                                     \
-            if (kv_waves == 8 && ml > 64) {                                                                                              \
-                set_smem(attn_bwd_dkdv_kernel<DD, 8>, smem_kv);                                                                          \
-                hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DD, 8>), dim3((ml + 127) / 128, Hkv * p.hs, ns), dim3(512), smem_kv, stream, p); \
-            } else {                                                                                                                     \
-                set_smem(attn_bwd_dkdv_kernel<DD, 4>, smem_kv);                                                                          \
-                hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DD, 4>), dim3((ml + 63) / 64, Hkv * p.hs, ns), dim3(256), smem_kv, stream, p);  \
-            }                                                                                                                            \
-            if (p.hs > 1) hipLaunchKernelGGL(attn_dkdv_reduce_kernel<DD>, dim3((ml * Hkv * 2 * (DD / 4) + 255) / 256, ns), dim3(256), 0, stream, p); \
-        }                                                                                                                                \
-    } while (0)
-    if (D == 128) LAUNCH_BWD(128); else LAUNCH_BWD(80);
-#undef LAUNCH_BWD
+    if (D == 128) launch_bwd<128>(p, o, delta, rg, nr, hs_all, stream);
+    else launch_bwd<80>(p, o, delta, rg, nr, hs_all, stream);
     return iadr1_check_launch("attn_bwd");
-}
-
-extern "C" int iadr1_attn_decode(const void* q, const void* kcache, const void* vcache, const int* block_table, const int* ctx_len, void* o,
-                                 int B, int Hq, int Hkv, int D, int max_pages, long long ldq, long long ldo, float scale, int seqs_per_group, const void* side, hipStream_t stream) {
-    IADR1_REQUIRE(D == 128, "attn_decode: head dim %d not built (128 is)", D);
-    IADR1_REQUIRE(B > 0 && Hq % Hkv == 0 && Hq / Hkv <= 16, "attn_decode: GQA group must be <= 16");
-    IADR1_REQUIRE((ldq % 8) == 0, "attn_decode: ldq must be a multiple of 8");
-    IADR1_REQUIRE(seqs_per_group >= 0 && (seqs_per_group <= 1 || B % seqs_per_group == 0), "attn_decode: B must be a multiple of seqs_per_group");
-    const int gseq = seqs_per_group > 1 ? seqs_per_group : 0;      // the blocks of a prompt group on one XCD: its L2 dedupes the shared prompt pages
-    DecodeArgs p{(const bf16_t*)q, (const bf16_t*)kcache, (const bf16_t*)vcache, block_table, ctx_len, (bf16_t*)o, ldq, ldo, B, Hq, Hkv, max_pages, scale, gseq};
-    const dim3 grid = gseq ? dim3(8 * ((B / gseq + 7) / 8) * gseq * Hkv) : dim3(B, Hkv);
-    // 16 waves per (sequence, kv head) block: a wave then walks ~1.5 pages instead of ~3 at ctx ~ 640 (the kernel is a chain of dependent
-    // page loads on only B*Hkv = 128 CUs)
-    constexpr int waves = 16;
-    const int gs = (Hq / Hkv <= 8) ? 9 : 17;
-    SideOut so;
-    if (int e = iadr1_side_arg(side, &so)) return e;
-    if (waves == 16) {
-        const int smem = (2 * 16 * 16 + 16 * 128 * gs) * 4;
-        set_smem(attn_decode_kernel<128, 16>, smem);
-        hipLaunchKernelGGL((attn_decode_kernel<128, 16>), grid, dim3(1024), smem, stream, p, so);
-    } else {
-        const int smem = (2 * 8 * 16 + 8 * 128 * gs) * 4;
-        set_smem(attn_decode_kernel<128, 8>, smem);
-        hipLaunchKernelGGL((attn_decode_kernel<128, 8>), grid, dim3(512), smem, stream, p, so);
-    }
-    return iadr1_check_launch("attn_decode");
-}
-
-extern "C" int iadr1_attn_decode_group(const void* q, const void* kcache, const void* vcache, const int* block_table, const int* ctx_len, const int* shared_pages, void* o,
-                                       int B, int G, int Hq, int Hkv, int D, int max_pages, long long ldq, long long ldo, float scale, int chunks, float* ws,
-                                       const void* side, hipStream_t stream) {
-    IADR1_REQUIRE(D == 128, "attn_decode_group: head dim %d not built (128 is)", D);
-    IADR1_REQUIRE(B > 0 && G >= 1 && (B % G) == 0 && Hq % Hkv == 0 && Hq / Hkv <= 16 && G * (Hq / Hkv) <= 64 && shared_pages != nullptr,
-                  "attn_decode_group: B must be a multiple of the group size and a group may hold at most 64 query rows per kv head (G=%d, heads per kv head=%d)", G, Hkv ? Hq / Hkv : 0);
-    IADR1_REQUIRE((ldq % 8) == 0 && (ldo % 4) == 0, "attn_decode_group: ldq must be a multiple of 8, ldo of 4");
-    IADR1_REQUIRE(chunks >= 1 && chunks <= 64 && (chunks == 1 || ws != nullptr), "attn_decode_group: 1 <= chunks <= 64, and chunks > 1 needs the workspace");
-    DecodeGroupArgs p{{(const bf16_t*)q, (const bf16_t*)kcache, (const bf16_t*)vcache, block_table, ctx_len, (bf16_t*)o, ldq, ldo, B, Hq, Hkv, max_pages, scale, 0}, shared_pages, G, 0, chunks, ws};
-    SideOut so, none{};
-    if (int e = iadr1_side_arg(side, &so)) return e;
-    const int rows = G * (Hq / Hkv), nt = rows <= 16 ? 1 : (rows <= 32 ? 2 : 4);
-    const int smem = (2 * 8 * 16 + 8 * 128 * 17 + 2 * 16 * nt + 16 * nt * 128) * 4 + nt * 4 * 64 * 8 * 2;       // reduction scratch, shared-part state, Q fragments
-    const dim3 block(512);
-    auto launch = [&](dim3 grid, const SideOut& s_) {
-        if (nt == 1) { set_smem(attn_decode_group_kernel<128, 1>, smem); hipLaunchKernelGGL((attn_decode_group_kernel<128, 1>), grid, block, smem, stream, p, s_); }
-        else if (nt == 2) { set_smem(attn_decode_group_kernel<128, 2>, smem); hipLaunchKernelGGL((attn_decode_group_kernel<128, 2>), grid, block, smem, stream, p, s_); }
-        else { set_smem(attn_decode_group_kernel<128, 4>, smem); hipLaunchKernelGGL((attn_decode_group_kernel<128, 4>), grid, block, smem, stream, p, s_); }
-    };
-    if (chunks == 1) {
-        launch(dim3(B / G, Hkv), so);
-    } else {
-        p.mode = 1;
-        launch(dim3(B / G, Hkv, chunks), none);
-        p.mode = 2;
-        launch(dim3(B / G, Hkv), so);
-    }
-    return iadr1_check_launch("attn_decode_group");
-}
-
-extern "C" int iadr1_kv_store(const void* k, long long ldk, const void* v, long long ldv, const long long* slot, void* kcache, void* vcache,
-                              int T, int Hkv, int D, hipStream_t stream) {
-    IADR1_REQUIRE(D == 128, "kv_store: head dim %d not built (128 is)", D);
-    IADR1_REQUIRE(T > 0 && (ldk % 8) == 0 && (ldv % 8) == 0, "kv_store: strides must be multiples of 8");
-    long long blocks = ((long long)T * Hkv * 16 + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(kv_store_kernel<128>, dim3((int)blocks), dim3(256), 0, stream, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, slot, (bf16_t*)kcache, (bf16_t*)vcache, T, Hkv);
-    return iadr1_check_launch("kv_store");
-}
-
-extern "C" int iadr1_rope_kv_store(void* qkv, long long ld, const float* cos_t, const float* sin_t, const long long* slot, void* kcache,
-                                   void* vcache, int T, int Hq, int Hkv, int D, hipStream_t stream) {
-    IADR1_REQUIRE(D == 128, "rope_kv_store: head dim %d not built (128 is)", D);
-    IADR1_REQUIRE(T > 0 && (ld % 8) == 0, "rope_kv_store: ld must be a multiple of 8");
-    const long long total = (long long)T * ((Hq + Hkv) * 16 + Hkv * 16);
-    long long blocks = (total + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(rope_kv_store_kernel<128>, dim3((int)blocks), dim3(256), 0, stream, (bf16_t*)qkv, ld, cos_t, sin_t, slot, (bf16_t*)kcache, (bf16_t*)vcache, T, Hq, Hkv);
-    return iadr1_check_launch("rope_kv_store");
 }
 
 IADR1_STAMPS_EXPORT(attn)
 #ifdef IADR1_STAMPS
 // probe builds only: blocks per CU the runtime admits for the attention kernels at their launch configuration
-extern "C" int iadr1_debug_attn_occupancy(int* out6) {
-    const int smem_kv = (2 * 32 * Cfg<128>::LD) * 2 + 64 * 4, smem_dq = (2 * 32 * Cfg<128>::LD) * 2, smem_f = (2 * 64 * Cfg<128>::LD) * 2;
-    hipOccupancyMaxActiveBlocksPerMultiprocessor(&out6[0], attn_bwd_dkdv_kernel<128, 4>, 256, smem_kv);
-    hipOccupancyMaxActiveBlocksPerMultiprocessor(&out6[1], attn_bwd_dkdv_kernel<128, 8>, 512, smem_kv);
-    hipOccupancyMaxActiveBlocksPerMultiprocessor(&out6[2], attn_bwd_dq_kernel<128, 1>, 256, smem_dq);
-    hipOccupancyMaxActiveBlocksPerMultiprocessor(&out6[3], attn_bwd_dq_kernel<128, 2>, 256, smem_dq);
-    hipOccupancyMaxActiveBlocksPerMultiprocessor(&out6[4], attn_fwd_kernel<128, 1>, 256, smem_f);
-    hipOccupancyMaxActiveBlocksPerMultiprocessor(&out6[5], attn_fwd_kernel<128, 2>, 256, smem_f);
+extern "C" int iadr1_debug_attn_occupancy(int* out5) {
+    hipOccupancyMaxActiveBlocksPerMultiprocessor(&out5[0], attn_bwd_dkdv_kernel<128, 4>, 256, DKDV_LDS);
+    hipOccupancyMaxActiveBlocksPerMultiprocessor(&out5[1], attn_bwd_dkdv_kernel<128, 8>, 512, DKDV_LDS);
+    hipOccupancyMaxActiveBlocksPerMultiprocessor(&out5[2], attn_bwd_dq_kernel<128, 1>, 256, DQ_LDS);
+    hipOccupancyMaxActiveBlocksPerMultiprocessor(&out5[3], attn_bwd_dq_kernel<128, 2>, 256, DQ_LDS);
+    hipOccupancyMaxActiveBlocksPerMultiprocessor(&out5[4], attn_fwd_kernel<128, 1>, 256, FWD_LDS);
     return 0;
 }
 #endif

@@ -38,10 +38,10 @@ m = ok & (nit >= 24)
 if m.any():
     for k, lab in enumerate(["barrier + register tile -> LDS + barrier (incl. waiting for the prefetched loads)", "S / dP: fragment reads + 16 MFMA", "softmax terms (exp, pack)", "dV / dK: transpose reads + 16 MFMA"]):
         print(f"  phase {k} {lab}: median {np.median(s[k][m] / 100.0 / nit[m]):.3f} us per iteration")
-occ = (ctypes.c_int * 6)()
+occ = (ctypes.c_int * 5)()
 L.iadr1_debug_attn_occupancy.argtypes, L.iadr1_debug_attn_occupancy.restype = [ctypes.c_void_p], ctypes.c_int
 L.iadr1_debug_attn_occupancy(occ)
-print("blocks per CU admitted (dkdv<4 waves>, dkdv<8 waves>, dq<R=1>, dq<R=2>, fwd<R=1>, fwd<R=2>):", list(occ))
+print("blocks per CU admitted (dkdv<4 waves>, dkdv<8 waves>, dq<R=1>, dq<R=2>, fwd):", list(occ))
 hv = ok & (nit >= 24)
 lt = ok & (nit < 24)
 base = t0[ok].min()

@@ -82,7 +82,7 @@ kcs = [torch.randn(npages, Hkv, 32, D, device=dev).to(torch.bfloat16) for _ in r
 vcs = [torch.randn(npages, Hkv, D, 32, device=dev).to(torch.bfloat16) for _ in range(4)]
 o = ops.PackedAct(M, Hq * D, dev)
 us = timeit(lambda i: ops.attn_decode(q_out[:, : Hq * D], kcs[i % 4], vcs[i % 4], bt, ctx, Hq, Hkv, D, D**-0.5, out=o), 4)
-report("attn_decode (ctx 640, 42 MB of K/V)", "attn", [0, 1, 2, 3], 128, ["entry -> pages done (table, K/V loads, MFMA)", "LDS exchange + barrier", "combine + stores"], us)
+report("attn_decode (ctx 640, 42 MB of K/V)", "attn_decode", [0, 1, 2, 3], 128, ["entry -> pages done (table, K/V loads, MFMA)", "LDS exchange + barrier", "combine + stores"], us)
 # ---- persistent gate|up with SwiGLU ---------------------------------------------------------------------------------------------------------------------
 gu = [ops.pack_gateup(torch.randn(2 * I, H, device=dev).to(torch.bfloat16)) for _ in range(NL)]
 a = ops.PackedAct(M, I, dev)

@@ -6,7 +6,7 @@
 //   (no temperature division), and == -CE for PA-SFT (TF:loss/loss_utils.py:32-71).
 // dlogits_rows: dlogit = g[row] * (onehot(target) - softmax(row)) in bf16, in a form ready for the two
 // backward GEMMs (dH = dlogits . W, dW = dlogits^T . H).
-// grpo_loss: sc_grpo_trainer.py:746,796-798,816 for one rank's [N,C] completion block.
+// grpo_loss: sc_grpo_trainer.py:746,796-798,816 for one rank's [N,C] completion block.  grpo_loss_is: the same with a truncated importance weight per token.
 #include "common.h"
 
 namespace {
@@ -96,6 +96,79 @@ __global__ __launch_bounds__(256) void grpo_loss_kernel(const float* logp, const
     }
 }
 
+// grpo_loss with a truncated importance weight per token (rollout / trainer log-prob mismatch).  d = logp - rollout_logp over the mask;
+//   level 0 (token):    w_i = min(exp(d_i), cap)          level 1 (sequence): w_i = min(exp(sum m d / cnt), cap) for every token of the row
+// w multiplies the whole per-token term (advantage and KL parts) and is a constant under differentiation; row_kl / kl_out stay unweighted.  Masked positions
+// (rollout_logp == 0 there by the rollout's contract) get d = 0 by a select and never reach an exp that feeds a sum.  With w == 1 every expression below rounds
+// as grpo_loss_kernel's does (1 * x is exact), so the four shared outputs are then bit-equal to that kernel's.
+// row_stats[n][5] = { sum m w, live tokens whose untruncated ratio exceeded cap, sum m |d|, max m |d|, sum m (exp(d) - d - 1) }.
+__global__ __launch_bounds__(256) void grpo_loss_is_kernel(const float* logp, const float* ref_logp, const float* rollout_logp, const float* adv,
+                                                           const int* mask, float beta, float cap, int level, float inv_nrows, float* dlogp,
+                                                           float* kl_out, float* row_loss, float* row_kl, float* w_out, float* row_stats, int N, int C) {
+    __shared__ float scratch[16];
+    const int n = blockIdx.x;
+    const float A = adv[n];
+    float cnt = 0.f, sd = 0.f;
+    for (int c = threadIdx.x; c < C; c += 256) {
+        const int i = n * C + c;
+        const int live = mask[i] != 0;
+        cnt += (float)mask[i];
+        sd += live ? logp[i] - rollout_logp[i] : 0.f;
+    }
+    cnt = block_sum<256>(cnt, scratch);
+    sd = block_sum<256>(sd, scratch);
+    const float inv = cnt > 0.f ? 1.f / cnt : 0.f;
+    const float ratio_row = __expf(sd * inv);
+    const float w_row = ratio_row > cap ? cap : ratio_row;
+    float sl = 0.f, sk = 0.f, sw = 0.f, nclip = 0.f, sabs = 0.f, mabs = 0.f, sk3 = 0.f;
+    for (int c = threadIdx.x; c < C; c += 256) {
+        const int i = n * C + c;
+        const float d = ref_logp[i] - logp[i];
+        const float e = __expf(d);
+        const float kl = e - d - 1.f;
+        const float m = (float)mask[i];
+        if (kl_out) kl_out[i] = kl;
+        const int live = mask[i] != 0;
+        const float dq = live ? logp[i] - rollout_logp[i] : 0.f;
+        const float ratio = __expf(dq);
+        const float w = level == 0 ? (ratio > cap ? cap : ratio) : w_row;
+        const float t = -(A - beta * kl);
+        sl += m * (w * t);
+        sk += m * kl;
+        if (live) {
+            sw += w;
+            nclip += (level == 0 ? ratio : ratio_row) > cap ? 1.f : 0.f;
+            sabs += fabsf(dq);
+            mabs = fmaxf(mabs, fabsf(dq));
+            sk3 += ratio - dq - 1.f;
+        }
+    }
+    sl = block_sum<256>(sl, scratch);
+    sk = block_sum<256>(sk, scratch);
+    sw = block_sum<256>(sw, scratch);
+    nclip = block_sum<256>(nclip, scratch);
+    sabs = block_sum<256>(sabs, scratch);
+    mabs = block_max<256>(mabs, scratch);
+    sk3 = block_sum<256>(sk3, scratch);
+    if (threadIdx.x == 0) {
+        row_loss[n] = sl * inv;
+        row_kl[n] = sk * inv;
+        float* st = row_stats + (long long)n * 5;
+        st[0] = sw; st[1] = nclip; st[2] = sabs; st[3] = mabs; st[4] = sk3;
+    }
+    for (int c = threadIdx.x; c < C; c += 256) {
+        const int i = n * C + c;
+        const float d = ref_logp[i] - logp[i];
+        const int live = mask[i] != 0;
+        const float ratio = __expf(live ? logp[i] - rollout_logp[i] : 0.f);
+        const float w = level == 0 ? (ratio > cap ? cap : ratio) : w_row;
+        // grpo_loss_kernel's expression, then the weight: the product by w stays outside so that nothing of the unweighted value is contracted differently
+        const float g = (float)mask[i] * inv * inv_nrows * (-A + beta * (1.f - __expf(d)));
+        dlogp[i] = w * g;
+        if (w_out) w_out[i] = live ? w : 0.f;
+    }
+}
+
 }  // namespace
 
 extern "C" int iadr1_logprob_rows(const float* logits, long long ld, const long long* targets, float* logp, float* lse, int R, int V,
@@ -117,4 +190,17 @@ extern "C" int iadr1_grpo_loss(const float* logp, const float* ref_logp, const f
     IADR1_REQUIRE(N > 0 && C > 0 && n_total_rows >= N, "grpo_loss: need 0 < N <= n_total_rows");
     hipLaunchKernelGGL(grpo_loss_kernel, dim3(N), dim3(256), 0, stream, logp, ref_logp, adv, mask, beta, 1.f / (float)n_total_rows, dlogp, kl, row_loss, row_kl, N, C);
     return iadr1_check_launch("grpo_loss");
+}
+extern "C" int iadr1_grpo_loss_is(const float* logp, const float* ref_logp, const float* rollout_logp, const float* adv, const int* mask, float beta,
+                                  float cap, int level, int n_total_rows, float* dlogp, float* kl, float* row_loss, float* row_kl, float* w_out,
+                                  float* row_stats, int N, int C, hipStream_t stream) {
+    IADR1_REQUIRE(N > 0, "grpo_loss_is: N must be > 0 (got %d)", N);
+    IADR1_REQUIRE(rollout_logp != nullptr, "grpo_loss_is: rollout_logp is null (the weight needs the rollout's log-probs)");
+    IADR1_REQUIRE(cap >= 1.f && cap <= 3.402823466e38f /* false for NaN and +inf */, "grpo_loss_is: cap must be finite and >= 1 (got %g): a smaller cap would down-weight on-policy tokens", (double)cap);
+    IADR1_REQUIRE(level == 0 || level == 1, "grpo_loss_is: unknown level %d (0 = token, 1 = sequence)", level);
+    IADR1_REQUIRE(C > 0 && n_total_rows >= N, "grpo_loss_is: need C > 0 and N <= n_total_rows");
+    IADR1_REQUIRE(row_stats != nullptr, "grpo_loss_is: row_stats is null");
+    hipLaunchKernelGGL(grpo_loss_is_kernel, dim3(N), dim3(256), 0, stream, logp, ref_logp, rollout_logp, adv, mask, beta, cap, level,
+                       1.f / (float)n_total_rows, dlogp, kl, row_loss, row_kl, w_out, row_stats, N, C);
+    return iadr1_check_launch("grpo_loss_is");
 }

@@ -600,6 +600,27 @@ def grpo_loss(logp, ref_logp, adv, mask, beta, n_total_rows=None):
     return dlogp, kl, row_loss, row_kl
 
 
+IS_LEVELS = {"token": 0, "sequence": 1}
+
+
+def grpo_loss_is(logp, ref_logp, rollout_logp, adv, mask, beta, cap, level="token", n_total_rows=None):
+    """iadr1_grpo_loss_is: grpo_loss with the truncated importance weight min(exp(logp - rollout_logp), cap) per token ("token") or per row ("sequence").
+    Returns (dlogp, kl, row_loss, row_kl, w [N, C], row_stats [N, 5]); the columns of row_stats are named in include/iadr1_hip.h."""
+    if level not in IS_LEVELS:
+        raise ValueError(f"grpo_loss_is: level must be one of {sorted(IS_LEVELS)}, got {level!r}")
+    N, C = logp.shape
+    dev = logp.device
+    dlogp = torch.empty(N, C, dtype=F32, device=dev)
+    kl = torch.empty(N, C, dtype=F32, device=dev)
+    row_loss = torch.empty(N, dtype=F32, device=dev)
+    row_kl = torch.empty(N, dtype=F32, device=dev)
+    w = torch.empty(N, C, dtype=F32, device=dev)
+    stats = torch.empty(N, 5, dtype=F32, device=dev)
+    hip.call("grpo_loss_is", logp, ref_logp, rollout_logp, adv, mask, float(beta), float(cap), IS_LEVELS[level], int(n_total_rows or N), dlogp, kl, row_loss, row_kl,
+             w, stats, N, C)
+    return dlogp, kl, row_loss, row_kl, w, stats
+
+
 _sample_ws = {}
 
 

@@ -12,6 +12,7 @@ this at per_device_train_batch_size=1, the only setting its scripts use (SURVEY.
 """
 from __future__ import annotations
 
+import math
 import os
 import sys
 
@@ -43,6 +44,12 @@ class GRPOArgs:
     # the rollout also returns the log-prob of every token it sampled (temperature 1, unfiltered: the quantity the loss scores); the step's metrics gain
     # rollout/logp_abs_diff_mean, rollout/logp_abs_diff_max and rollout/kl against the policy log-probs of the loss.  Nothing in the loss or the gradients changes.
     rollout_logps: bool = False
+    # truncated importance weight against the rollout's log-probs (0 = off: the loss does not read them).  cap >= 1: every per-token loss term is multiplied by
+    # w = min(exp(scored - sampled), cap), per token ("token") or with the row's mean log-ratio ("sequence"); w is a constant under differentiation
+    # (iadr1_grpo_loss_is).  Implies what rollout_logps asks of the rollout; the rollout/* metrics then come from the kernel's partials, plus rollout/is_weight_mean
+    # and rollout/is_clipped_frac.  Corrects the sampler-engine / trainer mismatch only (both sides temperature 1, unfiltered), not the temperature or top-k / top-p.
+    rollout_is_cap: float = 0.0
+    rollout_is_level: str = "token"
     learning_rate: float = 1e-6
     weight_decay: float = 0.0
     adam_beta1: float = 0.9
@@ -70,6 +77,10 @@ class GRPOArgs:
     # `--gradient_checkpointing` (REF scripts/train/SC_GRPO/*.sh:56): "off" | "auto" | "on" -- vlm.Engine.recompute_wanted.  With recomputation the policy's
     # forward is run after the rollout (the rollout's own activations are not kept either)
     recompute: str = "off"
+
+    @property
+    def wants_rollout_logps(self) -> bool:
+        return self.rollout_logps or self.rollout_is_cap > 0
 
 
 def eos_completion_mask(completion_ids: np.ndarray, eos_token_id: int) -> np.ndarray:
@@ -316,8 +327,15 @@ class SCGRPOEngine:
     def __init__(self, cfg: VLMConfig, policy: ParamStore, ref: ParamStore, args: GRPOArgs, group=None):
         if args.top_k <= 0 and args.top_p != 1.0:
             raise ValueError(f"GRPOArgs.top_k <= 0 samples the whole vocabulary and needs top_p == 1.0 (got top_p = {args.top_p}): a nucleus over all tokens is not built")
+        if args.rollout_is_cap != 0 and not (math.isfinite(args.rollout_is_cap) and args.rollout_is_cap >= 1.0):
+            raise ValueError(f"GRPOArgs.rollout_is_cap must be 0 (off) or a finite value >= 1 (got {args.rollout_is_cap}): a cap below 1 would down-weight on-policy tokens")
+        if args.rollout_is_level not in ops.IS_LEVELS:
+            raise ValueError(f"GRPOArgs.rollout_is_level must be one of {sorted(ops.IS_LEVELS)} (got {args.rollout_is_level!r})")
+        if args.rollout_is_cap > 0 and cfg.is_llava and args.llava_rotate_right_padded_rows:
+            raise ValueError("GRPOArgs.rollout_is_cap with llava_rotate_right_padded_rows: that path scores a rotated window, whose columns do not line up with the "
+                             "rollout's log-probs; set llava_rotate_right_padded_rows=False to weight the completion tokens themselves")
         self.cfg, self.args = cfg, args
-        self.last_rollout_logps = None      # [N, C] device tensor of the last rollout when args.rollout_logps
+        self.last_rollout_logps = None      # [N, C] device tensor of the last rollout when args.wants_rollout_logps
         self.pol, self.ref = Engine(policy), Engine(ref)
         self.dev = policy.device
         self.reducer = GradReducer(policy, group)
@@ -395,9 +413,9 @@ class SCGRPOEngine:
                 print("[iadr1] sequential step: the frozen reference's pass runs after the rollout, on the whole device", file=sys.stderr, flush=True)
         toks = self._rollout.generate(plan, img_pol, a.num_generations, a.max_completion_length, temperature=0.0 if greedy else a.temperature,
                                       top_k=a.top_k, top_p=a.top_p, seed=a.seed + 1000003 * self.opt_step + 7919 * self.accum, suppress_eos=a.suppress_eos,
-                                      train_carry=train_carry, train_trace=trace, shadow=shadow, return_logps=a.rollout_logps)
+                                      train_carry=train_carry, train_trace=trace, shadow=shadow, return_logps=a.wants_rollout_logps)
         self.last_rollout_logps = None
-        if a.rollout_logps:
+        if a.wants_rollout_logps:
             toks, self.last_rollout_logps = toks
         if shadow is not None:
             self.shadow_logps = shadow.logp
@@ -450,8 +468,11 @@ class SCGRPOEngine:
         ref_logps: [N, C] reference log-probs already computed for exactly these completions by the rollout's shadow pass (rollout(shadow_ref=True)): the
         reference forward is then not run here; the shadow stream is joined right before the loss kernel reads them.
         rollout_logps: [N, >= C] log-probs the rollout's sampler returned for exactly these completions (rollout with args.rollout_logps): compared with the policy
-        log-probs computed here over the completion mask (metrics rollout/*, result "rollout_logps"); the loss does not read them."""
+        log-probs computed here over the completion mask (metrics rollout/*, result "rollout_logps").  The loss reads them only with args.rollout_is_cap > 0: every
+        per-token term is then weighted by min(exp(scored - sampled), cap) (iadr1_grpo_loss_is; result "rollout_is_weights", metrics rollout/is_weight_mean and
+        rollout/is_clipped_frac), and completions without their rollout log-probs are refused."""
         a, c = self.args, self.cfg
+        use_is = a.rollout_is_cap > 0
         G = a.num_generations
         ids_p, mask_p = np.asarray(batch["input_ids"]), np.asarray(batch["attention_mask"])
         if a.max_prompt_length is not None:
@@ -461,6 +482,9 @@ class SCGRPOEngine:
         comp = completions if isinstance(completions, np.ndarray) else right_pad(completions, c.pad_token_id)
         assert comp.shape[0] == N
         C = comp.shape[1]
+        if use_is and (rollout_logps is None or rollout_logps.shape[0] != N or rollout_logps.shape[1] < C):
+            raise ValueError(f"GRPOArgs.rollout_is_cap > 0 needs the rollout log-probs of these [{N}, {C}] completions (rollout_logps=...): "
+                             f"got {None if rollout_logps is None else tuple(rollout_logps.shape)}")
         cmask = eos_completion_mask(comp, c.eos_token_id)
         ids = np.concatenate([np.repeat(ids_p, G, 0), comp], 1)
         mask = np.concatenate([np.repeat(mask_p, G, 0), cmask.astype(mask_p.dtype)], 1)
@@ -493,6 +517,10 @@ class SCGRPOEngine:
         kl_all = torch.empty(N, C, dtype=F32, device=self.dev)
         row_loss = torch.empty(N, dtype=F32, device=self.dev)
         row_kl = torch.empty(N, dtype=F32, device=self.dev)
+        if use_is:
+            ro_all = rollout_logps[:, :C].to(F32)
+            w_all = torch.empty(N, C, dtype=F32, device=self.dev)
+            is_stats = torch.empty(N, 5, dtype=F32, device=self.dev)
         mb = max(1, min(a.micro_batch_seqs, N))
         # shared-prefix layout (vlm.Engine.text_plan_shared): every prompt runs through the layers once per group instead of
         # G times -- needs micro-batches made of whole groups.  IADR1_SHARE_PREFIX=0 keeps the reference's [n, P+C] rows.
@@ -560,7 +588,11 @@ class SCGRPOEngine:
                 if si == 0:
                     self._shadow.join()          # the tail chunk of the shadow pass ran next to the policy's lm_head; everything after this reads its log-probs
                 rl = ref_logps[r0:r1].contiguous()
-            dlogp, kl, rloss, rkl = ops.grpo_loss(lp.view(n, C), rl.view(n, C), adv_d[r0:r1].contiguous(), cmask_d[r0:r1].contiguous(), a.beta, n_total_rows=N)
+            if use_is:
+                dlogp, kl, rloss, rkl, w_all[r0:r1], is_stats[r0:r1] = ops.grpo_loss_is(lp.view(n, C), rl.view(n, C), ro_all[r0:r1].contiguous(), adv_d[r0:r1].contiguous(),
+                                                                                      cmask_d[r0:r1].contiguous(), a.beta, a.rollout_is_cap, a.rollout_is_level, n_total_rows=N)
+            else:
+                dlogp, kl, rloss, rkl = ops.grpo_loss(lp.view(n, C), rl.view(n, C), adv_d[r0:r1].contiguous(), cmask_d[r0:r1].contiguous(), a.beta, n_total_rows=N)
             logp_all[r0:r1], ref_all[r0:r1], kl_all[r0:r1] = lp.view(n, C), rl.view(n, C), kl
             row_loss[r0:r1], row_kl[r0:r1] = rloss, rkl
             if backward:
@@ -577,7 +609,13 @@ class SCGRPOEngine:
         metrics = {"completion_length": float(cmask.sum(1).mean()), "reward": float(st["rewards"].mean()), "reward_std": float(st["std"].mean())}
         means = [row_loss.mean(), row_kl.mean()]
         ro_lp = None
-        if rollout_logps is not None:
+        if use_is:
+            # the same three rollout/* means from the loss kernel's per-row partials (columns: include/iadr1_hip.h), plus the mean weight and the clipped share
+            ro_lp = ro_all
+            cnt = float(max(1, int(cmask.sum())))
+            sums = is_stats.sum(0) / cnt
+            means += [sums[2], is_stats[:, 3].max(), sums[4], sums[0], sums[1]]
+        elif rollout_logps is not None:
             # sampled (the rollout's logits) vs scored (the policy forward of the loss) log-probs of the same tokens, over the completion mask; k3 estimator of
             # KL(sampled || scored) in the form iadr1_grpo_loss uses for policy vs reference: exp(d) - d - 1 with d = scored - sampled
             ro_lp = rollout_logps[:, :C].to(F32)
@@ -592,6 +630,8 @@ class SCGRPOEngine:
             metrics.update(loss=lk[0], kl=lk[1])
             if ro_lp is not None:
                 metrics.update({"rollout/logp_abs_diff_mean": lk[2], "rollout/logp_abs_diff_max": lk[3], "rollout/kl": lk[4]})
+            if use_is:
+                metrics.update({"rollout/is_weight_mean": lk[5], "rollout/is_clipped_frac": lk[6]})
             return metrics
         if defer_metrics:      # the caller enqueues more work (the optimizer) before it reads the two device-side means: no idle GPU while the host comes back from the sync
             metrics["finalize"] = finalize
@@ -601,6 +641,8 @@ class SCGRPOEngine:
                "rewards_per_func": st["rpf"], "ids": ids, "mask": mask}
         if ro_lp is not None:
             out["rollout_logps"] = ro_lp
+        if use_is:
+            out["rollout_is_weights"] = w_all
         return out
 
     # ---- optimizer -------------------------------------------------------------------------------------------------
@@ -660,7 +702,8 @@ class SCGRPOEngine:
         last_micro_step (default: do_optimizer_step): the data-parallel gradient buckets leave from this call's backward.
         completions: [N, C] ids already rolled out for these prompts (SCGRPOTrainer.training_step rolls all micro-batches of an optimizer step out at once): no
         rollout here, the policy forward runs over the completions.
-        rollout_logps: with `completions`, the log-probs their rollout returned for these rows (args.rollout_logps; SCGRPOTrainer.training_step's batched rollouts).
+        rollout_logps: with `completions`, the log-probs their rollout returned for these rows (args.rollout_logps; SCGRPOTrainer.training_step's batched rollouts);
+        required with args.rollout_is_cap > 0.
         return_outputs: the whole loss_and_grads dict (log-probs, advantages, masks, ids, metrics) plus "completion_ids" instead of the metrics alone."""
         import time
         timing = os.environ.get("IADR1_TIMING") == "1"
@@ -670,6 +713,8 @@ class SCGRPOEngine:
                 torch.cuda.synchronize()
             return time.perf_counter()
 
+        if completions is not None and rollout_logps is None and self.args.rollout_is_cap > 0:
+            raise ValueError("GRPOArgs.rollout_is_cap > 0: completions were handed in without their rollout log-probs (rollout_logps=...)")
         t0 = mark()
         vis = self.vision_policy(batch, save=True)
         t1 = mark()
@@ -685,7 +730,7 @@ class SCGRPOEngine:
         comp = self.rollout(batch, vis=vis, train_carry=carry, shadow_ref=True) if completions is None else np.asarray(completions)
         ref_lp = self.shadow_logps if completions is None else None
         pol_head = self.shadow_policy_head if completions is None else None
-        ro_lp = (self.last_rollout_logps if completions is None else rollout_logps) if self.args.rollout_logps else None
+        ro_lp = (self.last_rollout_logps if completions is None else rollout_logps) if self.args.wants_rollout_logps else None
         t2 = mark()
         # rewards are computed on the host inside loss_and_grads, after the first forward passes are in the GPU queue (in the
         # phase-timing mode they are evaluated here so that they get their own column)

@@ -44,6 +44,8 @@ class GRPOConfig:
     top_k: int = 50                 # (vLLM SamplingParams of REF sc_grpo_trainer.py:353-358: top_k 50, top_p 0.9); <= 0: the whole vocabulary, needs top_p 1.0
     top_p: float = 0.9
     rollout_logps: bool = False     # log rollout/logp_abs_diff_mean|max and rollout/kl: sampled vs scored log-probs of the rollout's tokens (GRPOArgs.rollout_logps)
+    rollout_is_cap: float = 0.0     # > 0 (then >= 1): weight every per-token loss term by min(exp(scored - sampled log-prob), cap); 0 = off (GRPOArgs.rollout_is_cap)
+    rollout_is_level: str = "token"     # "token" | "sequence" (one weight per row, from the row's mean log-ratio)
     learning_rate: float = 1e-6
     weight_decay: float = 0.0
     adam_beta1: float = 0.9
@@ -387,7 +389,8 @@ class SCGRPOTrainer:
             group = dist.group.WORLD
         self.engine = SCGRPOEngine(self.cfg, self.policy, self.ref, GRPOArgs(
             num_generations=args.num_generations, max_prompt_length=args.max_prompt_length, max_completion_length=args.max_completion_length,
-            beta=args.beta, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, rollout_logps=args.rollout_logps, learning_rate=args.learning_rate, weight_decay=args.weight_decay,
+            beta=args.beta, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, rollout_logps=args.rollout_logps, rollout_is_cap=args.rollout_is_cap, rollout_is_level=args.rollout_is_level,
+            learning_rate=args.learning_rate, weight_decay=args.weight_decay,
             adam_beta1=args.adam_beta1, adam_beta2=args.adam_beta2, adam_epsilon=args.adam_epsilon, max_grad_norm=args.max_grad_norm,
             gradient_accumulation_steps=args.gradient_accumulation_steps, micro_batch_seqs=args.micro_batch_seqs, seed=args.seed,
             # under data parallelism the policy is "auto" even without the flag: it recomputes only where the static budget (which then reserves RCCL's buffers) is tight
@@ -480,7 +483,7 @@ class SCGRPOTrainer:
             if "finalize" in m:
                 m.pop("finalize")()
             self._metrics["kl"].append(m["kl"])
-            for k in ("rollout/logp_abs_diff_mean", "rollout/logp_abs_diff_max", "rollout/kl"):
+            for k in ("rollout/logp_abs_diff_mean", "rollout/logp_abs_diff_max", "rollout/kl", "rollout/is_weight_mean", "rollout/is_clipped_frac"):
                 if k in m:
                     self._metrics[k].append(m[k])
             return m["loss"]
@@ -518,7 +521,7 @@ class SCGRPOTrainer:
             if both is not None:
                 G = self.args.num_generations
                 toks = self.engine.rollout(both)
-                all_lp = self.engine.last_rollout_logps      # None unless GRPOConfig.rollout_logps
+                all_lp = self.engine.last_rollout_logps      # None unless GRPOConfig.rollout_logps or rollout_is_cap
                 comps, lps, r = [], [], 0
                 for b in ready:
                     n = len(b["input_ids"]) * G

@@ -279,6 +279,20 @@ int iadr1_linear_logprob_dlogits(const void* H, const void* W, const long long* 
 /* n_total_rows: number of sequences the batch mean runs over (>= N when the step is micro-batched) */
 int iadr1_grpo_loss(const float* logp, const float* ref_logp, const float* adv, const int* mask, float beta, int n_total_rows,
                     float* dlogp, float* kl, float* row_loss, float* row_kl, int N, int C, iadr1_stream_t stream);
+/* grpo_loss_is: iadr1_grpo_loss with a truncated importance weight per token against the rollout's log-probs (the sampler's and the loss's kernels -- and,
+ * with FP8 decode weights, their weights -- differ, so the scored tokens are slightly off-policy).  Over the mask m, with d_i = logp_i - rollout_logp_i:
+ *   level 0 (token):    w_i = min(exp(d_i), cap)        level 1 (sequence): w_i = min(exp(sum_i m_i d_i / cnt), cap), one value per row
+ *   per-token loss  w_i * (-(A - beta * kl_i)),  row_loss = sum m_i * that / cnt,  dlogp_i = m_i / cnt / n_total_rows * w_i * (-A + beta * (1 - exp(ref_i - logp_i)))
+ * w is a constant under differentiation; kl and row_kl stay unweighted.  Both log-probs are temperature-1, unfiltered (iadr1_sample_logp's logp_out against
+ * iadr1_logprob_rows): the ratio corrects the engine mismatch, not the sampler's temperature / top-k / top-p filter.  rollout_logp at m_i == 0 is never exponentiated.
+ * With rollout_logp == logp bitwise the four shared outputs are bit-equal to iadr1_grpo_loss's.
+ *   w_out (may be NULL): [N, C], 0 where the mask is 0.
+ *   row_stats: [N, 5] per-row partials { sum m w, live tokens whose untruncated ratio exceeded cap, sum m |d|, max m |d|, sum m (exp(d) - d - 1) }.
+ * One block per row, fixed-order block reductions, no float atomics: run-to-run bit-identical.  Refused on the host: N <= 0, rollout_logp NULL, cap < 1 or not
+ * finite, level not in {0, 1}. */
+int iadr1_grpo_loss_is(const float* logp, const float* ref_logp, const float* rollout_logp, const float* adv, const int* mask, float beta, float cap,
+                       int level, int n_total_rows, float* dlogp, float* kl, float* row_loss, float* row_kl, float* w_out, float* row_stats, int N, int C,
+                       iadr1_stream_t stream);
 
 /* ---- optimizer (HF Trainer default AdamW + clip_grad_norm_, TF:trainer.py:1168) ------------------------------- */
 /* out[0] = sum(g^2), deterministic (fixed-order two-stage reduction; scratch = 2048 floats) so that data-parallel

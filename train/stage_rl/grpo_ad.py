@@ -83,6 +83,10 @@ def build_parser():
     p.add_argument("--top_p", type=float, default=0.9)
     p.add_argument("--rollout_logps", nargs="?", default=False, const=True, type=lambda v: str(v).lower() in ("1", "true", "yes"),
                    help="log rollout/logp_abs_diff_mean|max and rollout/kl: the sampler's log-probs of the tokens it drew against the loss's policy log-probs")
+    p.add_argument("--rollout_is_cap", type=float, default=0.0,
+                   help="> 0 (then >= 1): weight every per-token loss term by min(exp(scored - sampled log-prob), cap), the truncated importance weight against the "
+                        "rollout's log-probs (e.g. with --decode_weights fp8); 0 = off")
+    p.add_argument("--rollout_is_level", default="token", choices=["token", "sequence"], help="one weight per token, or one per completion from its mean log-ratio")
     p.add_argument("--learning_rate", type=float, default=1e-6)
     p.add_argument("--weight_decay", type=float, default=0.0)
     p.add_argument("--max_grad_norm", type=float, default=1.0)

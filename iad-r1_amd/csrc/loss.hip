@@ -21,11 +21,13 @@ __global__ __launch_bounds__(256) void logprob_rows_kernel(const float* logits, 
     for (int i = threadIdx.x; i < n4; i += 256) {
         const f32x4_t v = *(const f32x4_t*)(x + i * 4);
         const float mx = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+        if (mx == -INFINITY) continue;      // a group of masked (-inf) logits adds nothing; with m still -inf, exp(-inf - -inf) would be NaN
         if (mx > m) { s *= __expf(m - mx); m = mx; }
         s += __expf(v[0] - m) + __expf(v[1] - m) + __expf(v[2] - m) + __expf(v[3] - m);
     }
     for (int i = n4 * 4 + threadIdx.x; i < V; i += 256) {
         const float v = x[i];
+        if (v == -INFINITY) continue;
         if (v > m) { s *= __expf(m - v); m = v; }
         s += __expf(v - m);
     }

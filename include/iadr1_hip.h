@@ -260,7 +260,9 @@ int iadr1_rope_kv_store(void* qkv, long long ld, const float* cos_t, const float
 /* ---- log-probs / losses -----------------------------------------------------------------------------------
  * logprob_rows: REF:train/stage_rl/trainer/sc_grpo_trainer.py:510-513 (log_softmax + gather, no temperature)
  * and PA-SFT cross entropy TF:loss/loss_utils.py:32-71 (logp = -CE; target < 0 is ignored).
- * dlogits_rows: g[row] * (onehot - softmax) in bf16.   grpo_loss: REF:...sc_grpo_trainer.py:746,796-798,816. */
+ * dlogits_rows: g[row] * (onehot - softmax) in bf16.   grpo_loss: REF:...sc_grpo_trainer.py:746,796-798,816.
+ * -inf logits (masked vocabulary entries) are legal in both: such an id has probability 0 -- it adds nothing to lse, its dlogit is 0, and a target that
+ * points at it gets logp = -inf.  A row must hold at least one finite logit; +inf and NaN logits are not supported. */
 int iadr1_logprob_rows(const float* logits, long long ld, const long long* targets, float* logp, float* lse, int R, int V,
                        iadr1_stream_t stream);
 int iadr1_dlogits_rows(const float* logits, long long ld, const long long* targets, const float* lse, const float* g,

@@ -7,6 +7,7 @@
 // dlogits_rows: dlogit = g[row] * (onehot(target) - softmax(row)) in bf16, in a form ready for the two
 // backward GEMMs (dH = dlogits . W, dW = dlogits^T . H).
 // grpo_loss: sc_grpo_trainer.py:746,796-798,816 for one rank's [N,C] completion block.  grpo_loss_is: the same with a truncated importance weight per token.
+// grpo_loss_clip: the clipped surrogate of trl's GRPOTrainer (trl/trl/trainer/grpo_trainer.py:1203-1213) for optimizer steps that reuse a rollout (num_iterations > 1).
 #include "common.h"
 
 namespace {
@@ -171,6 +172,81 @@ __global__ __launch_bounds__(256) void grpo_loss_is_kernel(const float* logp, co
     }
 }
 
+// grpo_loss with the clipped surrogate against OLD log-probs (a rollout scored once, then used for several optimizer steps).  d = logp - old_logp over the mask;
+//   r = exp(d),  rc = clamp(r, 1 - eps_low, 1 + eps_high),  s = min(r A, rc A),  per-token loss  w (-(s - beta kl)),  w = 1 without w[]
+// A token is clipped when the min took the clamped (constant) branch: r < 1 - eps_low with A < 0, or r > 1 + eps_high with A > 0 (both strict); its advantage
+// term then has no gradient.  w (grpo_loss_is's w_out of the step that sampled) is a constant under differentiation; row_kl / kl_out stay unweighted.  Masked
+// positions get d = 0 by a select: old_logp there may hold anything (NaN included) and never reaches a sum.  On policy (old_logp == logp bitwise) r = rc = 1
+// and s = A exactly, so every expression below rounds as grpo_loss_is_kernel's (and, with w == 1, grpo_loss_kernel's) does: the products r * A sit behind a
+// min / a select, where nothing contracts them into the sums that follow.
+// row_stats[n][4] = { low-clipped live tokens, high-clipped live tokens, sum m r, max m |d| }.
+__global__ __launch_bounds__(256) void grpo_loss_clip_kernel(const float* logp, const float* old_logp, const float* ref_logp, const float* adv, const int* mask,
+                                                             const float* w_in, float beta, float lo, float hi, float inv_nrows, float* dlogp, float* kl_out,
+                                                             float* row_loss, float* row_kl, float* row_stats, int N, int C) {
+    __shared__ float scratch[16];
+    const int n = blockIdx.x;
+    const float A = adv[n];
+    float cnt = 0.f, sl = 0.f, sk = 0.f, nlo = 0.f, nhi = 0.f, sr = 0.f, mabs = 0.f;
+    for (int c = threadIdx.x; c < C; c += 256) {
+        const int i = n * C + c;
+        const float d = ref_logp[i] - logp[i];
+        const float e = __expf(d);
+        const float kl = e - d - 1.f;
+        const float m = (float)mask[i];
+        if (kl_out) kl_out[i] = kl;
+        const int live = mask[i] != 0;
+        const float dq = live ? logp[i] - old_logp[i] : 0.f;
+        const float r = __expf(dq);
+        const float rc = fminf(fmaxf(r, lo), hi);
+        const float s = fminf(r * A, rc * A);
+        const float w = w_in ? w_in[i] : 1.f;
+        const float t = -(s - beta * kl);
+        cnt += m;
+        sl += m * (w * t);
+        sk += m * kl;
+        if (live) {
+            nlo += (r < lo && A < 0.f) ? 1.f : 0.f;
+            nhi += (r > hi && A > 0.f) ? 1.f : 0.f;
+            sr += r;
+            mabs = fmaxf(mabs, fabsf(dq));
+        }
+    }
+    cnt = block_sum<256>(cnt, scratch);
+    sl = block_sum<256>(sl, scratch);
+    sk = block_sum<256>(sk, scratch);
+    nlo = block_sum<256>(nlo, scratch);
+    nhi = block_sum<256>(nhi, scratch);
+    sr = block_sum<256>(sr, scratch);
+    mabs = block_max<256>(mabs, scratch);
+    const float inv = cnt > 0.f ? 1.f / cnt : 0.f;
+    if (threadIdx.x == 0) {
+        row_loss[n] = sl * inv;
+        row_kl[n] = sk * inv;
+        float* st = row_stats + (long long)n * 4;
+        st[0] = nlo; st[1] = nhi; st[2] = sr; st[3] = mabs;
+    }
+    for (int c = threadIdx.x; c < C; c += 256) {
+        const int i = n * C + c;
+        const float d = ref_logp[i] - logp[i];
+        const int live = mask[i] != 0;
+        const float r = __expf(live ? logp[i] - old_logp[i] : 0.f);
+        const bool clipped = (r < lo && A < 0.f) || (r > hi && A > 0.f);
+        // d/dp min(r A, rc A) = r A where the unclamped branch is the min, 0 where the clamped one is
+        const float ga = clipped ? 0.f : r * A;
+        const float w = w_in ? w_in[i] : 1.f;
+        // grpo_loss_kernel's expression with r A for A, then the weight (as in grpo_loss_is_kernel).  Both of those compile -A + beta (1 - e) to a rounded product
+        // and a subtraction (the two products of the line pair up into packed multiplies, which leaves nothing to contract); the select in front of ga would let
+        // this one become an fma, one rounding fewer, so contraction is switched off for it
+        float g;
+        {
+#pragma clang fp contract(off)
+            const float bk = beta * (1.f - __expf(d));
+            g = (float)mask[i] * inv * inv_nrows * (bk - ga);
+        }
+        dlogp[i] = w * g;
+    }
+}
+
 }  // namespace
 
 extern "C" int iadr1_logprob_rows(const float* logits, long long ld, const long long* targets, float* logp, float* lse, int R, int V,
@@ -205,4 +281,17 @@ extern "C" int iadr1_grpo_loss_is(const float* logp, const float* ref_logp, cons
     hipLaunchKernelGGL(grpo_loss_is_kernel, dim3(N), dim3(256), 0, stream, logp, ref_logp, rollout_logp, adv, mask, beta, cap, level,
                        1.f / (float)n_total_rows, dlogp, kl, row_loss, row_kl, w_out, row_stats, N, C);
     return iadr1_check_launch("grpo_loss_is");
+}
+extern "C" int iadr1_grpo_loss_clip(const float* logp, const float* old_logp, const float* ref_logp, const float* adv, const int* mask, const float* w,
+                                    float beta, float eps_low, float eps_high, int n_total_rows, float* dlogp, float* kl, float* row_loss, float* row_kl,
+                                    float* row_stats, int N, int C, hipStream_t stream) {
+    IADR1_REQUIRE(N > 0, "grpo_loss_clip: N must be > 0 (got %d)", N);
+    IADR1_REQUIRE(old_logp != nullptr, "grpo_loss_clip: old_logp is null (the ratio needs the log-probs of the policy that sampled)");
+    IADR1_REQUIRE(row_stats != nullptr, "grpo_loss_clip: row_stats is null");
+    IADR1_REQUIRE(eps_low >= 0.f && eps_low < 1.f /* false for NaN */, "grpo_loss_clip: eps_low must be in [0, 1) (got %g)", (double)eps_low);
+    IADR1_REQUIRE(eps_high >= 0.f && eps_high <= 3.402823466e38f /* false for NaN and +inf */, "grpo_loss_clip: eps_high must be finite and >= 0 (got %g)", (double)eps_high);
+    IADR1_REQUIRE(C > 0 && n_total_rows >= N, "grpo_loss_clip: need C > 0 and N <= n_total_rows");
+    hipLaunchKernelGGL(grpo_loss_clip_kernel, dim3(N), dim3(256), 0, stream, logp, old_logp, ref_logp, adv, mask, w, beta, 1.f - eps_low, 1.f + eps_high,
+                       1.f / (float)n_total_rows, dlogp, kl, row_loss, row_kl, row_stats, N, C);
+    return iadr1_check_launch("grpo_loss_clip");
 }

@@ -621,6 +621,21 @@ def grpo_loss_is(logp, ref_logp, rollout_logp, adv, mask, beta, cap, level="toke
     return dlogp, kl, row_loss, row_kl, w, stats
 
 
+def grpo_loss_clip(logp, old_logp, ref_logp, adv, mask, beta, eps_low, eps_high, w=None, n_total_rows=None):
+    """iadr1_grpo_loss_clip: the clipped surrogate -min(r A, clamp(r, 1 - eps_low, 1 + eps_high) A) + beta kl with r = exp(logp - old_logp), every per-token term
+    times w [N, C] when given.  Returns (dlogp, kl, row_loss, row_kl, row_stats [N, 4]); the columns of row_stats are named in include/iadr1_hip.h."""
+    N, C = logp.shape
+    dev = logp.device
+    dlogp = torch.empty(N, C, dtype=F32, device=dev)
+    kl = torch.empty(N, C, dtype=F32, device=dev)
+    row_loss = torch.empty(N, dtype=F32, device=dev)
+    row_kl = torch.empty(N, dtype=F32, device=dev)
+    stats = torch.empty(N, 4, dtype=F32, device=dev)
+    hip.call("grpo_loss_clip", logp, old_logp, ref_logp, adv, mask, w, float(beta), float(eps_low), float(eps_high), int(n_total_rows or N), dlogp, kl, row_loss,
+             row_kl, stats, N, C)
+    return dlogp, kl, row_loss, row_kl, stats
+
+
 _sample_ws = {}
 
 

@@ -6,6 +6,9 @@ one MI355X per rank:
   advantages (per-prompt groups, rank-local)  ->  frozen-ref log-probs  ->  policy log-probs + backward  ->
   bucketed gradient all-reduce over RCCL (overlapped with the tail of backward)  ->  fused AdamW.
 
+With GRPOArgs.num_iterations > 1 the caller reuses a rollout for that many optimizer steps: the steps after the first hand the completions back with the
+log-probs the first one scored (old_logps), and the loss is trl's clipped surrogate (iadr1_grpo_loss_clip; REF trl/trl/trainer/grpo_trainer.py:1203-1213).
+
 Ordering: sequences are laid out prompt-major (p0 x G, p1 x G, ...) everywhere, i.e. the interleaved order the
 reference's reward / advantage code assumes (REF:754,775-792); its tensor tiling (REF:625-628) coincides with
 this at per_device_train_batch_size=1, the only setting its scripts use.
@@ -50,6 +53,13 @@ class GRPOArgs:
     # and rollout/is_clipped_frac.  Corrects the sampler-engine / trainer mismatch only (both sides temperature 1, unfiltered), not the temperature or top-k / top-p.
     rollout_is_cap: float = 0.0
     rollout_is_level: str = "token"
+    # trl.GRPOConfig's names and defaults (REF trl/trl/trainer/grpo_config.py; the reference's SC-GRPO path never sets them, so reuse is off by default).
+    # num_iterations (mu) > 1: the caller (SCGRPOTrainer.training_step) uses every rollout for mu consecutive optimizer steps; steps 1 .. mu-1 hand the log-probs
+    # iteration 0 scored back as old_logps, and the loss is the clipped surrogate -min(r A, clamp(r, 1 - epsilon, 1 + epsilon_high) A) + beta kl with
+    # r = exp(logp - old_logp) (iadr1_grpo_loss_clip; REF trl/trl/trainer/grpo_trainer.py:1203-1210).  epsilon_high None: epsilon.
+    num_iterations: int = 1
+    epsilon: float = 0.2
+    epsilon_high: float | None = None
     learning_rate: float = 1e-6
     weight_decay: float = 0.0
     adam_beta1: float = 0.9
@@ -81,6 +91,16 @@ class GRPOArgs:
     @property
     def wants_rollout_logps(self) -> bool:
         return self.rollout_logps or self.rollout_is_cap > 0
+
+
+def check_reuse_args(who: str, num_iterations, epsilon, epsilon_high):
+    """num_iterations / epsilon / epsilon_high of GRPOArgs and GRPOConfig (`who` names the class in the message)."""
+    if not (isinstance(num_iterations, int) and num_iterations >= 1):
+        raise ValueError(f"{who}.num_iterations must be an integer >= 1 (got {num_iterations!r})")
+    if not (math.isfinite(epsilon) and 0.0 <= epsilon < 1.0):
+        raise ValueError(f"{who}.epsilon must be finite and in [0, 1) (got {epsilon}): the lower clip bound 1 - epsilon of a probability ratio must stay positive")
+    if epsilon_high is not None and not (math.isfinite(epsilon_high) and epsilon_high >= 0.0):
+        raise ValueError(f"{who}.epsilon_high must be None (= epsilon) or finite and >= 0 (got {epsilon_high})")
 
 
 def eos_completion_mask(completion_ids: np.ndarray, eos_token_id: int) -> np.ndarray:
@@ -334,6 +354,7 @@ class SCGRPOEngine:
         if args.rollout_is_cap > 0 and cfg.is_llava and args.llava_rotate_right_padded_rows:
             raise ValueError("GRPOArgs.rollout_is_cap with llava_rotate_right_padded_rows: that path scores a rotated window, whose columns do not line up with the "
                              "rollout's log-probs; set llava_rotate_right_padded_rows=False to weight the completion tokens themselves")
+        check_reuse_args("GRPOArgs", args.num_iterations, args.epsilon, args.epsilon_high)
         self.cfg, self.args = cfg, args
         self.last_rollout_logps = None      # [N, C] device tensor of the last rollout when args.wants_rollout_logps
         self.pol, self.ref = Engine(policy), Engine(ref)
@@ -462,7 +483,7 @@ class SCGRPOEngine:
 
     # ---- loss + gradients for given completions ------------------------------------------------------------------
     def loss_and_grads(self, batch, completions, rewards_per_func, backward: bool = True, last_micro_step: bool = True, vis=None, train_carry=None, defer_metrics: bool = False,
-                       ref_logps=None, policy_head=None, rollout_logps=None):
+                       ref_logps=None, policy_head=None, rollout_logps=None, old_logps=None, is_weights=None):
         """completions: list of Bp*G id lists (prompt-major) or an [N,C] array already padded;
         rewards_per_func: [N, n_funcs] float tensor/array.  Accumulates gradients into policy.grad.
         ref_logps: [N, C] reference log-probs already computed for exactly these completions by the rollout's shadow pass (rollout(shadow_ref=True)): the
@@ -470,9 +491,15 @@ class SCGRPOEngine:
         rollout_logps: [N, >= C] log-probs the rollout's sampler returned for exactly these completions (rollout with args.rollout_logps): compared with the policy
         log-probs computed here over the completion mask (metrics rollout/*, result "rollout_logps").  The loss reads them only with args.rollout_is_cap > 0: every
         per-token term is then weighted by min(exp(scored - sampled), cap) (iadr1_grpo_loss_is; result "rollout_is_weights", metrics rollout/is_weight_mean and
-        rollout/is_clipped_frac), and completions without their rollout log-probs are refused."""
+        rollout/is_clipped_frac), and completions without their rollout log-probs are refused.
+        old_logps: [N, C] policy log-probs an earlier call returned as "logps" for exactly these completions (a reuse iteration of GRPOArgs.num_iterations > 1): the
+        loss is then the clipped surrogate against them (iadr1_grpo_loss_clip with args.epsilon / epsilon_high), the rollout/* metrics are not produced, and the
+        metrics gain clip_ratio/low_mean, clip_ratio/high_mean, clip_ratio/region_mean (shares of this call's live tokens), policy/ratio_mean and
+        policy/logp_abs_diff_max; result "old_logps".  With args.rollout_is_cap > 0 it needs is_weights, the "rollout_is_weights" of that earlier call: the weight of
+        the sampling engine against the policy that sampled does not change while its rollout is reused."""
         a, c = self.args, self.cfg
-        use_is = a.rollout_is_cap > 0
+        use_clip = old_logps is not None
+        use_is = a.rollout_is_cap > 0 and not use_clip
         G = a.num_generations
         ids_p, mask_p = np.asarray(batch["input_ids"]), np.asarray(batch["attention_mask"])
         if a.max_prompt_length is not None:
@@ -485,6 +512,15 @@ class SCGRPOEngine:
         if use_is and (rollout_logps is None or rollout_logps.shape[0] != N or rollout_logps.shape[1] < C):
             raise ValueError(f"GRPOArgs.rollout_is_cap > 0 needs the rollout log-probs of these [{N}, {C}] completions (rollout_logps=...): "
                              f"got {None if rollout_logps is None else tuple(rollout_logps.shape)}")
+        if use_clip:
+            if tuple(old_logps.shape) != (N, C):
+                raise ValueError(f"old_logps must be the [{N}, {C}] log-probs scored for these completions, got {tuple(old_logps.shape)}")
+            w_clip = None
+            if a.rollout_is_cap > 0:
+                if is_weights is None or tuple(is_weights.shape) != (N, C):
+                    raise ValueError(f"GRPOArgs.rollout_is_cap > 0: a reuse iteration (old_logps=...) needs is_weights, the [{N}, {C}] rollout_is_weights of the step that "
+                                     f"sampled these completions: got {None if is_weights is None else tuple(is_weights.shape)}")
+                w_clip = is_weights.to(F32)
         cmask = eos_completion_mask(comp, c.eos_token_id)
         ids = np.concatenate([np.repeat(ids_p, G, 0), comp], 1)
         mask = np.concatenate([np.repeat(mask_p, G, 0), cmask.astype(mask_p.dtype)], 1)
@@ -508,6 +544,7 @@ class SCGRPOEngine:
             vis = self.vision_policy(batch, save=backward)
         grids, plan_v, px, rows, img_pol, vctx = vis["grids"], vis["plan"], vis["px"], vis["rows"], vis["img"], vis["ctx"]
         have_ref = ref_logps is not None and tuple(ref_logps.shape) == (N, C)
+        shadowed = have_ref and ref_logps is self.shadow_logps      # this step's rollout ran the shadow pass that wrote them (else: handed in by the caller, nothing to join)
         img_ref = None if have_ref else self.ref.vision_forward(px, plan_v, save=False)[0]
         gpr, off = self._per_row_images(batch, grids, rows)
         dimg32 = torch.zeros(img_pol.shape, dtype=F32, device=self.dev) if backward else None
@@ -521,6 +558,10 @@ class SCGRPOEngine:
             ro_all = rollout_logps[:, :C].to(F32)
             w_all = torch.empty(N, C, dtype=F32, device=self.dev)
             is_stats = torch.empty(N, 5, dtype=F32, device=self.dev)
+        if use_clip:
+            old_all = old_logps.to(F32)
+            eps_high = a.epsilon if a.epsilon_high is None else a.epsilon_high
+            clip_stats = torch.empty(N, 4, dtype=F32, device=self.dev)
         mb = max(1, min(a.micro_batch_seqs, N))
         # shared-prefix layout (vlm.Engine.text_plan_shared): every prompt runs through the layers once per group instead of
         # G times -- needs micro-batches made of whole groups.  IADR1_SHARE_PREFIX=0 keeps the reference's [n, P+C] rows.
@@ -585,10 +626,14 @@ class SCGRPOEngine:
                 self._shadow.join()
             adv_d = advantages()["adv_d"]
             if have_ref:
-                if si == 0:
+                if si == 0 and shadowed:
                     self._shadow.join()          # the tail chunk of the shadow pass ran next to the policy's lm_head; everything after this reads its log-probs
                 rl = ref_logps[r0:r1].contiguous()
-            if use_is:
+            if use_clip:
+                dlogp, kl, rloss, rkl, clip_stats[r0:r1] = ops.grpo_loss_clip(lp.view(n, C), old_all[r0:r1].contiguous(), rl.view(n, C), adv_d[r0:r1].contiguous(),
+                                                                              cmask_d[r0:r1].contiguous(), a.beta, a.epsilon, eps_high,
+                                                                              w=None if w_clip is None else w_clip[r0:r1].contiguous(), n_total_rows=N)
+            elif use_is:
                 dlogp, kl, rloss, rkl, w_all[r0:r1], is_stats[r0:r1] = ops.grpo_loss_is(lp.view(n, C), rl.view(n, C), ro_all[r0:r1].contiguous(), adv_d[r0:r1].contiguous(),
                                                                                       cmask_d[r0:r1].contiguous(), a.beta, a.rollout_is_cap, a.rollout_is_level, n_total_rows=N)
             else:
@@ -609,13 +654,18 @@ class SCGRPOEngine:
         metrics = {"completion_length": float(cmask.sum(1).mean()), "reward": float(st["rewards"].mean()), "reward_std": float(st["std"].mean())}
         means = [row_loss.mean(), row_kl.mean()]
         ro_lp = None
-        if use_is:
+        if use_clip:
+            # clipped shares, mean ratio and largest |logp - old_logp| over this call's live tokens, from the loss kernel's per-row partials
+            cnt = float(max(1, int(cmask.sum())))
+            sums = clip_stats.sum(0) / cnt
+            means += [sums[0], sums[1], sums[2], clip_stats[:, 3].max()]
+        elif use_is:
             # the same three rollout/* means from the loss kernel's per-row partials (columns: include/iadr1_hip.h), plus the mean weight and the clipped share
             ro_lp = ro_all
             cnt = float(max(1, int(cmask.sum())))
             sums = is_stats.sum(0) / cnt
             means += [sums[2], is_stats[:, 3].max(), sums[4], sums[0], sums[1]]
-        elif rollout_logps is not None:
+        elif rollout_logps is not None and not use_clip:
             # sampled (the rollout's logits) vs scored (the policy forward of the loss) log-probs of the same tokens, over the completion mask; k3 estimator of
             # KL(sampled || scored) in the form iadr1_grpo_loss uses for policy vs reference: exp(d) - d - 1 with d = scored - sampled
             ro_lp = rollout_logps[:, :C].to(F32)
@@ -628,6 +678,9 @@ class SCGRPOEngine:
         def finalize():
             lk = dev_means.tolist()
             metrics.update(loss=lk[0], kl=lk[1])
+            if use_clip:
+                metrics.update({"clip_ratio/low_mean": lk[2], "clip_ratio/high_mean": lk[3], "clip_ratio/region_mean": lk[2] + lk[3], "policy/ratio_mean": lk[4],
+                                "policy/logp_abs_diff_max": lk[5]})
             if ro_lp is not None:
                 metrics.update({"rollout/logp_abs_diff_mean": lk[2], "rollout/logp_abs_diff_max": lk[3], "rollout/kl": lk[4]})
             if use_is:
@@ -643,6 +696,8 @@ class SCGRPOEngine:
             out["rollout_logps"] = ro_lp
         if use_is:
             out["rollout_is_weights"] = w_all
+        if use_clip:
+            out["old_logps"] = old_all
         return out
 
     # ---- optimizer -------------------------------------------------------------------------------------------------
@@ -695,7 +750,8 @@ class SCGRPOEngine:
             return False
         return shadow_cus(self.cfg, n_seq, self.args.max_completion_length) > 0
 
-    def _step(self, batch, reward_fn, do_optimizer_step=True, last_micro_step=None, return_outputs=False, defer_metrics=False, completions=None, rollout_logps=None):
+    def _step(self, batch, reward_fn, do_optimizer_step=True, last_micro_step=None, return_outputs=False, defer_metrics=False, completions=None, rollout_logps=None,
+              ref_logps=None, old_logps=None, is_weights=None):
         """One SC-GRPO micro-step: vision tower -> group rollout -> rewards -> reference / policy passes + backward (-> optimizer).  This is the path
         `SCGRPOTrainer.compute_loss` (the reference's API, REF:586) runs and the one bench.py times.
         reward_fn(completion_ids: np.ndarray [N,C]) -> [N, n_funcs] rewards (decode + plugin functions live with the caller, which owns the tokenizer).
@@ -704,6 +760,9 @@ class SCGRPOEngine:
         rollout here, the policy forward runs over the completions.
         rollout_logps: with `completions`, the log-probs their rollout returned for these rows (args.rollout_logps; SCGRPOTrainer.training_step's batched rollouts);
         required with args.rollout_is_cap > 0.
+        old_logps (with `completions`): a reuse iteration of args.num_iterations > 1 -- the "logps" the step that rolled these completions out returned, with its
+        "ref_logps" (no reference forward here) and, with args.rollout_is_cap > 0, its "rollout_is_weights" as is_weights in place of the rollout log-probs;
+        loss_and_grads then takes the clipped surrogate.
         return_outputs: the whole loss_and_grads dict (log-probs, advantages, masks, ids, metrics) plus "completion_ids" instead of the metrics alone."""
         import time
         timing = os.environ.get("IADR1_TIMING") == "1"
@@ -713,7 +772,11 @@ class SCGRPOEngine:
                 torch.cuda.synchronize()
             return time.perf_counter()
 
-        if completions is not None and rollout_logps is None and self.args.rollout_is_cap > 0:
+        if completions is None and (old_logps is not None or ref_logps is not None or is_weights is not None):
+            raise ValueError("old_logps / ref_logps / is_weights belong to completions that were rolled out earlier: hand those in too (completions=...)")
+        if completions is not None and old_logps is not None and is_weights is None and self.args.rollout_is_cap > 0:
+            raise ValueError("GRPOArgs.rollout_is_cap > 0: a reuse iteration (old_logps=...) needs the rollout_is_weights of the step that sampled (is_weights=...)")
+        if completions is not None and old_logps is None and rollout_logps is None and self.args.rollout_is_cap > 0:
             raise ValueError("GRPOArgs.rollout_is_cap > 0: completions were handed in without their rollout log-probs (rollout_logps=...)")
         t0 = mark()
         vis = self.vision_policy(batch, save=True)
@@ -728,7 +791,7 @@ class SCGRPOEngine:
             if self.pol.recompute_wanted(len(batch["input_ids"]) * P_ + N * a.max_completion_length, a.recompute):
                 carry = None       # gradient checkpointing: nothing of the rollout is kept, the policy forward runs (checkpointed) before backward
         comp = self.rollout(batch, vis=vis, train_carry=carry, shadow_ref=True) if completions is None else np.asarray(completions)
-        ref_lp = self.shadow_logps if completions is None else None
+        ref_lp = self.shadow_logps if completions is None else ref_logps
         pol_head = self.shadow_policy_head if completions is None else None
         ro_lp = (self.last_rollout_logps if completions is None else rollout_logps) if self.args.wants_rollout_logps else None
         t2 = mark()
@@ -739,8 +802,8 @@ class SCGRPOEngine:
         self.last_step_traced = bool(carry and carry.get("traced"))     # the decode steps filled the completion rows of the training arena
         last = do_optimizer_step if last_micro_step is None else last_micro_step
         out = self.loss_and_grads(batch, comp, rewards, backward=True, last_micro_step=last, vis=vis, train_carry=carry, defer_metrics=defer_metrics or do_optimizer_step,
-                                  ref_logps=ref_lp, policy_head=pol_head, rollout_logps=ro_lp)
-        self.last_step_shadowed = ref_lp is not None
+                                  ref_logps=ref_lp, policy_head=pol_head, rollout_logps=ro_lp, old_logps=old_logps, is_weights=is_weights)
+        self.last_step_shadowed = ref_lp is not None and completions is None
         t4 = mark()
         if do_optimizer_step:
             self.optimizer_step()

@@ -25,7 +25,7 @@ import torch
 
 from . import schedule
 from .params import ParamStore, VLMConfig
-from .sc_grpo import GRPOArgs, SCGRPOEngine
+from .sc_grpo import GRPOArgs, SCGRPOEngine, check_reuse_args
 
 
 @dataclass
@@ -46,6 +46,12 @@ class GRPOConfig:
     rollout_logps: bool = False     # log rollout/logp_abs_diff_mean|max and rollout/kl: sampled vs scored log-probs of the rollout's tokens (GRPOArgs.rollout_logps)
     rollout_is_cap: float = 0.0     # > 0 (then >= 1): weight every per-token loss term by min(exp(scored - sampled log-prob), cap); 0 = off (GRPOArgs.rollout_is_cap)
     rollout_is_level: str = "token"     # "token" | "sequence" (one weight per row, from the row's mean log-ratio)
+    # trl.GRPOConfig's names and defaults.  num_iterations (mu) > 1: every rollout serves mu consecutive optimizer steps (training_step); steps 1 .. mu-1 run no
+    # rollout, no reward function and no reference forward, and take the clipped surrogate -min(r A, clamp(r, 1 - epsilon, 1 + epsilon_high) A) + beta kl against
+    # the log-probs scored at step 0 (GRPOArgs.num_iterations).  The reference's scripts never set it: 1 is today's step.
+    num_iterations: int = 1
+    epsilon: float = 0.2
+    epsilon_high: Optional[float] = None    # None: epsilon
     learning_rate: float = 1e-6
     weight_decay: float = 0.0
     adam_beta1: float = 0.9
@@ -329,6 +335,10 @@ class SCGRPOTrainer:
             name = model if isinstance(model, str) else "model"
             args = GRPOConfig(output_dir=f"{os.path.basename(name.rstrip('/'))}-GRPO")
         self.args = args
+        check_reuse_args("GRPOConfig", args.num_iterations, args.epsilon, args.epsilon_high)
+        if args.save_steps and args.save_steps % args.num_iterations != 0:
+            raise ValueError(f"GRPOConfig.save_steps ({args.save_steps}) must be a multiple of num_iterations ({args.num_iterations}): a checkpoint holds no cached "
+                             "rollout, so a run can only continue from the first optimizer step of a generation")
         mik = args.model_init_kwargs or {}
         if isinstance(model, str):
             td = mik.get("torch_dtype")
@@ -390,7 +400,7 @@ class SCGRPOTrainer:
         self.engine = SCGRPOEngine(self.cfg, self.policy, self.ref, GRPOArgs(
             num_generations=args.num_generations, max_prompt_length=args.max_prompt_length, max_completion_length=args.max_completion_length,
             beta=args.beta, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, rollout_logps=args.rollout_logps, rollout_is_cap=args.rollout_is_cap, rollout_is_level=args.rollout_is_level,
-            learning_rate=args.learning_rate, weight_decay=args.weight_decay,
+            num_iterations=args.num_iterations, epsilon=args.epsilon, epsilon_high=args.epsilon_high, learning_rate=args.learning_rate, weight_decay=args.weight_decay,
             adam_beta1=args.adam_beta1, adam_beta2=args.adam_beta2, adam_epsilon=args.adam_epsilon, max_grad_norm=args.max_grad_norm,
             gradient_accumulation_steps=args.gradient_accumulation_steps, micro_batch_seqs=args.micro_batch_seqs, seed=args.seed,
             # under data parallelism the policy is "auto" even without the flag: it recomputes only where the static budget (which then reserves RCCL's buffers) is tight
@@ -398,6 +408,7 @@ class SCGRPOTrainer:
         self.state = type("State", (), {"global_step": 0})()
         self._metrics = defaultdict(list)
         self.log_history = []
+        self._generation = []               # num_iterations > 1: what the reuse steps of the current generation need, one entry per micro-batch (compute_loss)
         self._prefetcher = None
         self.prefetch_used = False          # a prefetch worker was started at some point (train() stops it again on the way out)
 
@@ -452,14 +463,22 @@ class SCGRPOTrainer:
 
     # ---- reference API ---------------------------------------------------------------------------------------------
     def compute_loss(self, model, inputs, return_outputs=False, num_items_in_batch=None, last_micro_step=True, _defer=False, _prepared=None, _batch=None, _completions=None,
-                     _rollout_logps=None):
+                     _rollout_logps=None, _reuse=None):
         """One SC-GRPO micro-step on `inputs` (list of dataset rows).  Returns the loss value; gradients are
         accumulated inside the engine (there is no autograd graph to hand back).
         _defer (training_step, last micro-batch): returns a callable that yields the loss once called -- the two device-side means (loss, KL) are then read
         AFTER the optimizer has been enqueued, so the GPU does not idle while the host returns from the read.
-        _prepared: a Future from `prefetch` for these same rows (the batch was built while the previous micro-batch ran); None: built here, as the reference does."""
+        _prepared: a Future from `prefetch` for these same rows (the batch was built while the previous micro-batch ran); None: built here, as the reference does.
+        _reuse: an entry of self._generation (a reuse step of num_iterations > 1): its batch, completions, old / reference log-probs, rewards and importance weights
+        are scored again under the current weights -- no rollout, no reward function, no reference forward; only `kl` and the clip_ratio/* / policy/* metrics are
+        appended (the generation's own metrics were logged once, at its first step; REF trl/trl/trainer/grpo_trainer.py:1100-1130 vs :1221-1244)."""
         if return_outputs:
             raise ValueError("The GRPOTrainer does not support returning outputs")  # REF:587-588
+        if _reuse is not None:
+            out = self.engine.step(_reuse["batch"], lambda comp: _reuse["rewards_per_func"], do_optimizer_step=False, last_micro_step=last_micro_step, return_outputs=True,
+                                   defer_metrics=_defer, completions=_reuse["completions"], ref_logps=_reuse["ref_logps"], old_logps=_reuse["old_logps"],
+                                   is_weights=_reuse["is_weights"])
+            return self._finish_metrics(out["metrics"], _defer)
         if _batch is not None:          # training_step already built it (and rolled the completions out with the other micro-batches of the step: _completions)
             batch = _batch
         elif _prepared is not None:
@@ -472,22 +491,33 @@ class SCGRPOTrainer:
         out = self.engine.step(batch, lambda comp: self._rewards(inputs, comp), do_optimizer_step=False, last_micro_step=last_micro_step, return_outputs=True, defer_metrics=_defer,
                                completions=_completions, rollout_logps=_rollout_logps)
         m = out["metrics"]
+        if self.args.num_iterations > 1:
+            # device tensors as the step returned them (no host round trip), cut to the longest completion of these rows like the batched rollout's (trim_completions)
+            # (not for the LLaVA families: their rotated scoring window depends on the row length, REF:516-567, so a reuse step keeps the columns step 0 scored)
+            comp = out["completion_ids"] if self.cfg.is_llava else trim_completions(out["completion_ids"], self.cfg.eos_token_id)
+            c = comp.shape[1]
+            w = out.get("rollout_is_weights")
+            self._generation.append({"batch": batch, "completions": comp, "old_logps": out["logps"][:, :c].contiguous(), "ref_logps": out["ref_logps"][:, :c].contiguous(),
+                                     "rewards_per_func": out["rewards_per_func"], "is_weights": None if w is None else w[:, :c].contiguous()})
         self._metrics["completion_length"].append(m["completion_length"])
         rp = out["rewards_per_func"].mean(0)
         for i, f in enumerate(self.reward_funcs):
             self._metrics[f"rewards/{reward_func_name(f)}"].append(float(rp[i]))
         self._metrics["reward"].append(m["reward"])
         self._metrics["reward_std"].append(m["reward_std"])
+        return self._finish_metrics(m, _defer)
 
+    def _finish_metrics(self, m, defer):
         def finish():
             if "finalize" in m:
                 m.pop("finalize")()
             self._metrics["kl"].append(m["kl"])
-            for k in ("rollout/logp_abs_diff_mean", "rollout/logp_abs_diff_max", "rollout/kl", "rollout/is_weight_mean", "rollout/is_clipped_frac"):
+            for k in ("rollout/logp_abs_diff_mean", "rollout/logp_abs_diff_max", "rollout/kl", "rollout/is_weight_mean", "rollout/is_clipped_frac",
+                      "clip_ratio/low_mean", "clip_ratio/high_mean", "clip_ratio/region_mean", "policy/ratio_mean", "policy/logp_abs_diff_max"):
                 if k in m:
                     self._metrics[k].append(m[k])
             return m["loss"]
-        return finish if _defer else finish()
+        return finish if defer else finish()
 
     def log(self, logs: dict, start_time=None):
         metrics = {k: sum(v) / len(v) for k, v in self._metrics.items()}
@@ -507,7 +537,20 @@ class SCGRPOTrainer:
     def training_step(self, micro_batches: list[list[dict]], prepared: Optional[list] = None) -> list[float]:
         """One optimizer step = gradient_accumulation_steps micro-batches through compute_loss (the data-parallel gradient buckets leave during the
         last one's backward) + clip / AdamW / weight-copy refresh.  What transformers.Trainer.training_step + the optimizer block of its inner loop do
-        around the reference's compute_loss (TF:trainer.py:1892-1961, :1785); train() and bench.py both go through here."""
+        around the reference's compute_loss (TF:trainer.py:1892-1961, :1785); train() and bench.py both go through here.
+        With num_iterations (mu) > 1 the call for optimizer step s = state.global_step with s % mu > 0 is a reuse step: it scores the micro-batches the generation's
+        first step kept (self._generation) again, under the clipped surrogate; `micro_batches` and `prepared` are not read."""
+        if self.state.global_step % self.args.num_iterations != 0:
+            if not self._generation:
+                raise RuntimeError(f"optimizer step {self.state.global_step} is a reuse step (num_iterations = {self.args.num_iterations}) but no rollout is cached: "
+                                   "a generation starts at a step that is a multiple of num_iterations")
+            last = len(self._generation) - 1
+            losses = [self.compute_loss(None, None, last_micro_step=(k == last), _defer=(k == last), _reuse=g) for k, g in enumerate(self._generation)]
+            self.engine.optimizer_step()
+            losses[last] = losses[last]()
+            self.state.global_step += 1
+            return losses
+        self._generation = []
         last = len(micro_batches) - 1
         ready = comps = lps = None
         rows_total = sum(len(mb) for mb in micro_batches) * self.args.num_generations
@@ -548,18 +591,23 @@ class SCGRPOTrainer:
             if ck is None:
                 raise ValueError(f"No valid checkpoint found in output directory ({a.output_dir})")
             st = load_training_state(self.policy, ck)
+            if st["global_step"] % a.num_iterations != 0:
+                raise ValueError(f"{ck}: written at optimizer step {st['global_step']}, inside a generation of num_iterations = {a.num_iterations} steps; the cached rollout "
+                                 "is not checkpointed, so a run can only resume at a multiple of num_iterations")
             self.engine.opt_step, self.state.global_step, start = st["opt_step"], st["global_step"], st["global_step"]
         rows = list(self.train_dataset)
         bs, ga = a.per_device_train_batch_size, a.gradient_accumulation_steps
         # prompts are sharded over ranks, each rank keeps whole groups.  Every rank derives the step count from the GLOBAL
         # row count and holds ceil(n / world) rows per epoch (wrap-around padding, as DistributedSampler): equal collective sequences on all ranks
-        total = schedule.total_steps(len(rows), world, bs, ga, a.num_train_epochs, a.max_steps)
+        # every generation (one pass of `ga` micro-batches over fresh rows) takes num_iterations optimizer steps; max_steps counts optimizer steps
+        mu = a.num_iterations
+        total = schedule.total_steps(len(rows), world, bs, ga, a.num_train_epochs, a.max_steps) * (1 if (a.max_steps and a.max_steps > 0) else mu)
         sampler = schedule.RankSampler(len(rows), rank, world, seed=a.seed, shuffle=a.shuffle)
         t0 = time.time()
-        steps_per_epoch = max(1, schedule.total_steps(len(rows), world, bs, ga, 1.0, -1))
+        steps_per_epoch = max(1, schedule.total_steps(len(rows), world, bs, ga, 1.0, -1)) * mu
 
         def micro_rows(step):      # the rows of optimizer step `step`: a function of the step number alone (the sampler order is fixed up front)
-            base = step * bs * ga
+            base = (step // mu) * bs * ga
             return [[rows[sampler.index(base + k * bs + j)] for j in range(bs)] for k in range(ga)]
 
         try:
@@ -569,13 +617,14 @@ class SCGRPOTrainer:
 
     def _train_loop(self, start, total, micro_rows, steps_per_epoch, rank, t0):
         a = self.args
+        mu = a.num_iterations
         window_loss, window_from = 0.0, start
         nxt = self.prefetch(micro_rows(start)) if (a.prefetch_batches and start < total) else None
         for step in range(start, total):
             self.engine.args.learning_rate = self._lr(step, total)
             micro, prepared = micro_rows(step), nxt
-            # step + 1's batches are built on the worker thread while this step runs on the GPU
-            nxt = self.prefetch(micro_rows(step + 1)) if (a.prefetch_batches and step + 1 < total) else None
+            # step + 1's batches are built on the worker thread while this step runs on the GPU (only when step + 1 rolls out: a reuse step reads no rows)
+            nxt = self.prefetch(micro_rows(step + 1)) if (a.prefetch_batches and step + 1 < total and (step + 1) % mu == 0) else None
             losses = self.training_step(micro, prepared)
             window_loss += float(np.mean(losses))
             if self.state.global_step % a.logging_steps == 0:

@@ -295,6 +295,21 @@ int iadr1_grpo_loss(const float* logp, const float* ref_logp, const float* adv, 
 int iadr1_grpo_loss_is(const float* logp, const float* ref_logp, const float* rollout_logp, const float* adv, const int* mask, float beta, float cap,
                        int level, int n_total_rows, float* dlogp, float* kl, float* row_loss, float* row_kl, float* w_out, float* row_stats, int N, int C,
                        iadr1_stream_t stream);
+/* grpo_loss_clip: the clipped surrogate of trl's GRPOTrainer (REF:trl/trl/trainer/grpo_trainer.py:1203-1213, loss_type "grpo") for optimizer steps that reuse a
+ * rollout (num_iterations > 1; REF:...grpo_trainer.py:741-755).  old_logp: the log-probs of the policy that sampled, scored once per generation (REF:995-1002).
+ * Over the mask m, with d_i = logp_i - old_logp_i, r_i = exp(d_i), rc_i = clamp(r_i, 1 - eps_low, 1 + eps_high):
+ *   per-token loss  w_i * (-(min(r_i A, rc_i A) - beta * kl_i)),  row_loss = sum m_i * that / cnt,  kl_i as in iadr1_grpo_loss
+ *   a token is clipped when r_i < 1 - eps_low and A < 0 (low) or r_i > 1 + eps_high and A > 0 (high), both strict
+ *   dlogp_i = m_i / cnt / n_total_rows * w_i * ((clipped ? 0 : -A r_i) + beta * (1 - exp(ref_i - logp_i)))
+ * w (may be NULL: 1): [N, C] per-token weights, constant under differentiation -- the w_out of the iadr1_grpo_loss_is call of the step that sampled; kl and
+ * row_kl stay unweighted.  old_logp at m_i == 0 may hold anything (NaN included): it is never exponentiated.  With old_logp == logp bitwise the four shared
+ * outputs are bit-equal to iadr1_grpo_loss's (w NULL) or to those of the iadr1_grpo_loss_is call whose w_out is passed as w.
+ *   row_stats: [N, 4] per-row partials { low-clipped live tokens, high-clipped live tokens, sum m r, max m |d| }.
+ * One block per row, fixed-order block reductions, no float atomics: run-to-run bit-identical.  Refused on the host: N <= 0, old_logp or row_stats NULL, eps_low
+ * not in [0, 1), eps_high < 0 or not finite, C <= 0, n_total_rows < N. */
+int iadr1_grpo_loss_clip(const float* logp, const float* old_logp, const float* ref_logp, const float* adv, const int* mask, const float* w /* may be NULL */,
+                         float beta, float eps_low, float eps_high, int n_total_rows, float* dlogp, float* kl, float* row_loss, float* row_kl,
+                         float* row_stats /* [N,4] */, int N, int C, iadr1_stream_t stream);
 
 /* ---- optimizer (HF Trainer default AdamW + clip_grad_norm_, TF:trainer.py:1168) ------------------------------- */
 /* out[0] = sum(g^2), deterministic (fixed-order two-stage reduction; scratch = 2048 floats) so that data-parallel

@@ -87,6 +87,10 @@ def build_parser():
                    help="> 0 (then >= 1): weight every per-token loss term by min(exp(scored - sampled log-prob), cap), the truncated importance weight against the "
                         "rollout's log-probs (e.g. with --decode_weights fp8); 0 = off")
     p.add_argument("--rollout_is_level", default="token", choices=["token", "sequence"], help="one weight per token, or one per completion from its mean log-ratio")
+    p.add_argument("--num_iterations", type=int, default=1,
+                   help="optimizer steps per rollout (trl's mu): steps after the first of a generation score the same completions again under the clipped surrogate")
+    p.add_argument("--epsilon", type=float, default=0.2, help="lower clip bound 1 - epsilon of the policy ratio (and the upper one unless --epsilon_high); read when --num_iterations > 1")
+    p.add_argument("--epsilon_high", type=float, default=None, help="upper clip bound 1 + epsilon_high; default: --epsilon")
     p.add_argument("--learning_rate", type=float, default=1e-6)
     p.add_argument("--weight_decay", type=float, default=0.0)
     p.add_argument("--max_grad_norm", type=float, default=1.0)

@@ -8,6 +8,7 @@
 // backward GEMMs (dH = dlogits . W, dW = dlogits^T . H).
 // grpo_loss: sc_grpo_trainer.py:746,796-798,816 for one rank's [N,C] completion block.  grpo_loss_is: the same with a truncated importance weight per token.
 // grpo_loss_clip: the clipped surrogate of trl's GRPOTrainer (trl/trl/trainer/grpo_trainer.py:1203-1213) for optimizer steps that reuse a rollout (num_iterations > 1).
+// grpo_loss_ex: the same three kernels behind one entry point, with the row normaliser of trl's loss_type (grpo_trainer.py:1212-1219) and an optional reference.
 #include "common.h"
 
 namespace {
@@ -63,10 +64,23 @@ __global__ __launch_bounds__(256) void dlogits_rows_kernel(const float* logits, 
     }
 }
 
+// ref_logp - logp of one token.  REF false (no reference model, beta == 0): the constant 0, so kl = exp(0) - 0 - 1 = 0 and the KL part of the gradient is
+// beta (1 - exp(0)) = 0 at compile time, and no load through ref_logp exists in that instantiation.
+template <bool REF>
+__device__ __forceinline__ float ref_gap(const float* ref_logp, const float* logp, int i) {
+    if constexpr (REF) return ref_logp[i] - logp[i];
+    else return 0.f;
+}
+
+// The three loss kernels share two parameters.  REF: see ref_gap.  row_scale: 0 = every row's sums are divided by its live-token count (inv = 1 / cnt, trl's
+// loss_type "grpo"); > 0 = this factor instead, the same for every row ("bnpo": rows / live tokens of the batch, "dr_grpo": 1 / max_completion_length).  It
+// replaces inv in row_loss and dlogp only: row_kl and the sequence-level importance ratio stay means over cnt.
+
 // One block per sequence row.  Outputs: dlogp [N,C] (gradient of the batch loss w.r.t. the policy
 // log-probs), per-token kl [N,C], and per-row partials row_loss[N], row_kl[N] (means over the mask).
+template <bool REF>
 __global__ __launch_bounds__(256) void grpo_loss_kernel(const float* logp, const float* ref_logp, const float* adv, const int* mask,
-                                                        float beta, float inv_nrows, float* dlogp, float* kl_out, float* row_loss,
+                                                        float beta, float inv_nrows, float row_scale, float* dlogp, float* kl_out, float* row_loss,
                                                         float* row_kl, int N, int C) {
     __shared__ float scratch[16];
     const int n = blockIdx.x;
@@ -74,7 +88,7 @@ __global__ __launch_bounds__(256) void grpo_loss_kernel(const float* logp, const
     float cnt = 0.f, sl = 0.f, sk = 0.f;
     for (int c = threadIdx.x; c < C; c += 256) {
         const int i = n * C + c;
-        const float d = ref_logp[i] - logp[i];
+        const float d = ref_gap<REF>(ref_logp, logp, i);
         const float e = __expf(d);
         const float kl = e - d - 1.f;
         const float m = (float)mask[i];
@@ -87,15 +101,16 @@ __global__ __launch_bounds__(256) void grpo_loss_kernel(const float* logp, const
     sl = block_sum<256>(sl, scratch);
     sk = block_sum<256>(sk, scratch);
     const float inv = cnt > 0.f ? 1.f / cnt : 0.f;
+    const float scale = row_scale > 0.f ? row_scale : inv;
     if (threadIdx.x == 0) {
-        row_loss[n] = sl * inv;
+        row_loss[n] = sl * scale;
         row_kl[n] = sk * inv;
     }
     for (int c = threadIdx.x; c < C; c += 256) {
         const int i = n * C + c;
-        const float d = ref_logp[i] - logp[i];
+        const float d = ref_gap<REF>(ref_logp, logp, i);
         // d/dp [ -(exp(p - sg p) A - beta (exp(r-p) - (r-p) - 1)) ] = -A + beta (1 - exp(r-p))
-        dlogp[i] = (float)mask[i] * inv * inv_nrows * (-A + beta * (1.f - __expf(d)));
+        dlogp[i] = (float)mask[i] * scale * inv_nrows * (-A + beta * (1.f - __expf(d)));
     }
 }
 
@@ -105,8 +120,9 @@ __global__ __launch_bounds__(256) void grpo_loss_kernel(const float* logp, const
 // (rollout_logp == 0 there by the rollout's contract) get d = 0 by a select and never reach an exp that feeds a sum.  With w == 1 every expression below rounds
 // as grpo_loss_kernel's does (1 * x is exact), so the four shared outputs are then bit-equal to that kernel's.
 // row_stats[n][5] = { sum m w, live tokens whose untruncated ratio exceeded cap, sum m |d|, max m |d|, sum m (exp(d) - d - 1) }.
+template <bool REF>
 __global__ __launch_bounds__(256) void grpo_loss_is_kernel(const float* logp, const float* ref_logp, const float* rollout_logp, const float* adv,
-                                                           const int* mask, float beta, float cap, int level, float inv_nrows, float* dlogp,
+                                                           const int* mask, float beta, float cap, int level, float inv_nrows, float row_scale, float* dlogp,
                                                            float* kl_out, float* row_loss, float* row_kl, float* w_out, float* row_stats, int N, int C) {
     __shared__ float scratch[16];
     const int n = blockIdx.x;
@@ -121,12 +137,13 @@ __global__ __launch_bounds__(256) void grpo_loss_is_kernel(const float* logp, co
     cnt = block_sum<256>(cnt, scratch);
     sd = block_sum<256>(sd, scratch);
     const float inv = cnt > 0.f ? 1.f / cnt : 0.f;
+    const float scale = row_scale > 0.f ? row_scale : inv;
     const float ratio_row = __expf(sd * inv);
     const float w_row = ratio_row > cap ? cap : ratio_row;
     float sl = 0.f, sk = 0.f, sw = 0.f, nclip = 0.f, sabs = 0.f, mabs = 0.f, sk3 = 0.f;
     for (int c = threadIdx.x; c < C; c += 256) {
         const int i = n * C + c;
-        const float d = ref_logp[i] - logp[i];
+        const float d = ref_gap<REF>(ref_logp, logp, i);
         const float e = __expf(d);
         const float kl = e - d - 1.f;
         const float m = (float)mask[i];
@@ -154,19 +171,19 @@ __global__ __launch_bounds__(256) void grpo_loss_is_kernel(const float* logp, co
     mabs = block_max<256>(mabs, scratch);
     sk3 = block_sum<256>(sk3, scratch);
     if (threadIdx.x == 0) {
-        row_loss[n] = sl * inv;
+        row_loss[n] = sl * scale;
         row_kl[n] = sk * inv;
         float* st = row_stats + (long long)n * 5;
         st[0] = sw; st[1] = nclip; st[2] = sabs; st[3] = mabs; st[4] = sk3;
     }
     for (int c = threadIdx.x; c < C; c += 256) {
         const int i = n * C + c;
-        const float d = ref_logp[i] - logp[i];
+        const float d = ref_gap<REF>(ref_logp, logp, i);
         const int live = mask[i] != 0;
         const float ratio = __expf(live ? logp[i] - rollout_logp[i] : 0.f);
         const float w = level == 0 ? (ratio > cap ? cap : ratio) : w_row;
         // grpo_loss_kernel's expression, then the weight: the product by w stays outside so that nothing of the unweighted value is contracted differently
-        const float g = (float)mask[i] * inv * inv_nrows * (-A + beta * (1.f - __expf(d)));
+        const float g = (float)mask[i] * scale * inv_nrows * (-A + beta * (1.f - __expf(d)));
         dlogp[i] = w * g;
         if (w_out) w_out[i] = live ? w : 0.f;
     }
@@ -180,8 +197,9 @@ __global__ __launch_bounds__(256) void grpo_loss_is_kernel(const float* logp, co
 // and s = A exactly, so every expression below rounds as grpo_loss_is_kernel's (and, with w == 1, grpo_loss_kernel's) does: the products r * A sit behind a
 // min / a select, where nothing contracts them into the sums that follow.
 // row_stats[n][4] = { low-clipped live tokens, high-clipped live tokens, sum m r, max m |d| }.
+template <bool REF>
 __global__ __launch_bounds__(256) void grpo_loss_clip_kernel(const float* logp, const float* old_logp, const float* ref_logp, const float* adv, const int* mask,
-                                                             const float* w_in, float beta, float lo, float hi, float inv_nrows, float* dlogp, float* kl_out,
+                                                             const float* w_in, float beta, float lo, float hi, float inv_nrows, float row_scale, float* dlogp, float* kl_out,
                                                              float* row_loss, float* row_kl, float* row_stats, int N, int C) {
     __shared__ float scratch[16];
     const int n = blockIdx.x;
@@ -189,7 +207,7 @@ __global__ __launch_bounds__(256) void grpo_loss_clip_kernel(const float* logp, 
     float cnt = 0.f, sl = 0.f, sk = 0.f, nlo = 0.f, nhi = 0.f, sr = 0.f, mabs = 0.f;
     for (int c = threadIdx.x; c < C; c += 256) {
         const int i = n * C + c;
-        const float d = ref_logp[i] - logp[i];
+        const float d = ref_gap<REF>(ref_logp, logp, i);
         const float e = __expf(d);
         const float kl = e - d - 1.f;
         const float m = (float)mask[i];
@@ -219,15 +237,16 @@ __global__ __launch_bounds__(256) void grpo_loss_clip_kernel(const float* logp, 
     sr = block_sum<256>(sr, scratch);
     mabs = block_max<256>(mabs, scratch);
     const float inv = cnt > 0.f ? 1.f / cnt : 0.f;
+    const float scale = row_scale > 0.f ? row_scale : inv;
     if (threadIdx.x == 0) {
-        row_loss[n] = sl * inv;
+        row_loss[n] = sl * scale;
         row_kl[n] = sk * inv;
         float* st = row_stats + (long long)n * 4;
         st[0] = nlo; st[1] = nhi; st[2] = sr; st[3] = mabs;
     }
     for (int c = threadIdx.x; c < C; c += 256) {
         const int i = n * C + c;
-        const float d = ref_logp[i] - logp[i];
+        const float d = ref_gap<REF>(ref_logp, logp, i);
         const int live = mask[i] != 0;
         const float r = __expf(live ? logp[i] - old_logp[i] : 0.f);
         const bool clipped = (r < lo && A < 0.f) || (r > hi && A > 0.f);
@@ -241,7 +260,7 @@ __global__ __launch_bounds__(256) void grpo_loss_clip_kernel(const float* logp, 
         {
 #pragma clang fp contract(off)
             const float bk = beta * (1.f - __expf(d));
-            g = (float)mask[i] * inv * inv_nrows * (bk - ga);
+            g = (float)mask[i] * scale * inv_nrows * (bk - ga);
         }
         dlogp[i] = w * g;
     }
@@ -266,7 +285,7 @@ extern "C" int iadr1_dlogits_rows(const float* logits, long long ld, const long 
 extern "C" int iadr1_grpo_loss(const float* logp, const float* ref_logp, const float* adv, const int* mask, float beta, int n_total_rows,
                                float* dlogp, float* kl, float* row_loss, float* row_kl, int N, int C, hipStream_t stream) {
     IADR1_REQUIRE(N > 0 && C > 0 && n_total_rows >= N, "grpo_loss: need 0 < N <= n_total_rows");
-    hipLaunchKernelGGL(grpo_loss_kernel, dim3(N), dim3(256), 0, stream, logp, ref_logp, adv, mask, beta, 1.f / (float)n_total_rows, dlogp, kl, row_loss, row_kl, N, C);
+    hipLaunchKernelGGL(grpo_loss_kernel<true>, dim3(N), dim3(256), 0, stream, logp, ref_logp, adv, mask, beta, 1.f / (float)n_total_rows, 0.f, dlogp, kl, row_loss, row_kl, N, C);
     return iadr1_check_launch("grpo_loss");
 }
 extern "C" int iadr1_grpo_loss_is(const float* logp, const float* ref_logp, const float* rollout_logp, const float* adv, const int* mask, float beta,
@@ -278,8 +297,8 @@ extern "C" int iadr1_grpo_loss_is(const float* logp, const float* ref_logp, cons
     IADR1_REQUIRE(level == 0 || level == 1, "grpo_loss_is: unknown level %d (0 = token, 1 = sequence)", level);
     IADR1_REQUIRE(C > 0 && n_total_rows >= N, "grpo_loss_is: need C > 0 and N <= n_total_rows");
     IADR1_REQUIRE(row_stats != nullptr, "grpo_loss_is: row_stats is null");
-    hipLaunchKernelGGL(grpo_loss_is_kernel, dim3(N), dim3(256), 0, stream, logp, ref_logp, rollout_logp, adv, mask, beta, cap, level,
-                       1.f / (float)n_total_rows, dlogp, kl, row_loss, row_kl, w_out, row_stats, N, C);
+    hipLaunchKernelGGL(grpo_loss_is_kernel<true>, dim3(N), dim3(256), 0, stream, logp, ref_logp, rollout_logp, adv, mask, beta, cap, level,
+                       1.f / (float)n_total_rows, 0.f, dlogp, kl, row_loss, row_kl, w_out, row_stats, N, C);
     return iadr1_check_launch("grpo_loss_is");
 }
 extern "C" int iadr1_grpo_loss_clip(const float* logp, const float* old_logp, const float* ref_logp, const float* adv, const int* mask, const float* w,
@@ -291,7 +310,47 @@ extern "C" int iadr1_grpo_loss_clip(const float* logp, const float* old_logp, co
     IADR1_REQUIRE(eps_low >= 0.f && eps_low < 1.f /* false for NaN */, "grpo_loss_clip: eps_low must be in [0, 1) (got %g)", (double)eps_low);
     IADR1_REQUIRE(eps_high >= 0.f && eps_high <= 3.402823466e38f /* false for NaN and +inf */, "grpo_loss_clip: eps_high must be finite and >= 0 (got %g)", (double)eps_high);
     IADR1_REQUIRE(C > 0 && n_total_rows >= N, "grpo_loss_clip: need C > 0 and N <= n_total_rows");
-    hipLaunchKernelGGL(grpo_loss_clip_kernel, dim3(N), dim3(256), 0, stream, logp, old_logp, ref_logp, adv, mask, w, beta, 1.f - eps_low, 1.f + eps_high,
-                       1.f / (float)n_total_rows, dlogp, kl, row_loss, row_kl, row_stats, N, C);
+    hipLaunchKernelGGL(grpo_loss_clip_kernel<true>, dim3(N), dim3(256), 0, stream, logp, old_logp, ref_logp, adv, mask, w, beta, 1.f - eps_low, 1.f + eps_high,
+                       1.f / (float)n_total_rows, 0.f, dlogp, kl, row_loss, row_kl, row_stats, N, C);
     return iadr1_check_launch("grpo_loss_clip");
+}
+// The three forms above behind one entry point: which one runs follows from which of old_logp / rollout_logp is given, REF from ref_logp, and row_scale is
+// handed through.  With ref_logp given and row_scale == 0 the launch is the old entry point's, argument for argument.
+extern "C" int iadr1_grpo_loss_ex(const float* logp, const float* ref_logp, const float* old_logp, const float* rollout_logp, const float* w, const float* adv,
+                                  const int* mask, float beta, float cap, int level, float eps_low, float eps_high, float row_scale, int n_total_rows, float* dlogp,
+                                  float* kl, float* row_loss, float* row_kl, float* w_out, float* row_stats, int N, int C, hipStream_t stream) {
+    IADR1_REQUIRE(N > 0, "grpo_loss_ex: N must be > 0 (got %d)", N);
+    IADR1_REQUIRE(C > 0, "grpo_loss_ex: C must be > 0 (got %d)", C);
+    IADR1_REQUIRE(n_total_rows >= N, "grpo_loss_ex: n_total_rows (%d) is smaller than N (%d): it is the row count of the whole step", n_total_rows, N);
+    IADR1_REQUIRE(ref_logp != nullptr || beta == 0.f, "grpo_loss_ex: ref_logp is null with beta = %g: the KL term needs the reference's log-probs (only beta == 0 runs without them)", (double)beta);
+    IADR1_REQUIRE(row_scale >= 0.f && row_scale <= 3.402823466e38f /* false for NaN and +inf */, "grpo_loss_ex: row_scale must be 0 (1 / live tokens of the row) or finite and > 0 (got %g)", (double)row_scale);
+    IADR1_REQUIRE(old_logp == nullptr || rollout_logp == nullptr, "grpo_loss_ex: old_logp and rollout_logp are both given: a reuse step takes the cached weights as w, not the rollout's log-probs");
+    IADR1_REQUIRE(w == nullptr || old_logp != nullptr, "grpo_loss_ex: w is given without old_logp (the weights belong to the clipped form)");
+    IADR1_REQUIRE(row_stats != nullptr || (old_logp == nullptr && rollout_logp == nullptr), "grpo_loss_ex: row_stats is null (the %s form writes [N, %d] partials)", old_logp ? "clip" : "IS", old_logp ? 4 : 5);
+    const float inv_nrows = 1.f / (float)n_total_rows;
+    if (old_logp != nullptr) {
+        IADR1_REQUIRE(eps_low >= 0.f && eps_low < 1.f /* false for NaN */, "grpo_loss_ex: eps_low must be in [0, 1) (got %g)", (double)eps_low);
+        IADR1_REQUIRE(eps_high >= 0.f && eps_high <= 3.402823466e38f /* false for NaN and +inf */, "grpo_loss_ex: eps_high must be finite and >= 0 (got %g)", (double)eps_high);
+        if (ref_logp != nullptr)
+            hipLaunchKernelGGL(grpo_loss_clip_kernel<true>, dim3(N), dim3(256), 0, stream, logp, old_logp, ref_logp, adv, mask, w, beta, 1.f - eps_low, 1.f + eps_high,
+                               inv_nrows, row_scale, dlogp, kl, row_loss, row_kl, row_stats, N, C);
+        else
+            hipLaunchKernelGGL(grpo_loss_clip_kernel<false>, dim3(N), dim3(256), 0, stream, logp, old_logp, ref_logp, adv, mask, w, beta, 1.f - eps_low, 1.f + eps_high,
+                               inv_nrows, row_scale, dlogp, kl, row_loss, row_kl, row_stats, N, C);
+    } else if (rollout_logp != nullptr) {
+        IADR1_REQUIRE(cap >= 1.f && cap <= 3.402823466e38f /* false for NaN and +inf */, "grpo_loss_ex: cap must be finite and >= 1 (got %g): a smaller cap would down-weight on-policy tokens", (double)cap);
+        IADR1_REQUIRE(level == 0 || level == 1, "grpo_loss_ex: unknown level %d (0 = token, 1 = sequence)", level);
+        if (ref_logp != nullptr)
+            hipLaunchKernelGGL(grpo_loss_is_kernel<true>, dim3(N), dim3(256), 0, stream, logp, ref_logp, rollout_logp, adv, mask, beta, cap, level, inv_nrows, row_scale,
+                               dlogp, kl, row_loss, row_kl, w_out, row_stats, N, C);
+        else
+            hipLaunchKernelGGL(grpo_loss_is_kernel<false>, dim3(N), dim3(256), 0, stream, logp, ref_logp, rollout_logp, adv, mask, beta, cap, level, inv_nrows, row_scale,
+                               dlogp, kl, row_loss, row_kl, w_out, row_stats, N, C);
+    } else {
+        if (ref_logp != nullptr)
+            hipLaunchKernelGGL(grpo_loss_kernel<true>, dim3(N), dim3(256), 0, stream, logp, ref_logp, adv, mask, beta, inv_nrows, row_scale, dlogp, kl, row_loss, row_kl, N, C);
+        else
+            hipLaunchKernelGGL(grpo_loss_kernel<false>, dim3(N), dim3(256), 0, stream, logp, ref_logp, adv, mask, beta, inv_nrows, row_scale, dlogp, kl, row_loss, row_kl, N, C);
+    }
+    return iadr1_check_launch("grpo_loss_ex");
 }

@@ -636,6 +636,31 @@ def grpo_loss_clip(logp, old_logp, ref_logp, adv, mask, beta, eps_low, eps_high,
     return dlogp, kl, row_loss, row_kl, stats
 
 
+def grpo_loss_ex(logp, adv, mask, beta, *, ref_logp=None, old_logp=None, rollout_logp=None, w=None, cap=0.0, level="token", eps_low=0.0, eps_high=0.0, row_scale=0.0,
+                 n_total_rows=None):
+    """iadr1_grpo_loss_ex: grpo_loss (neither old_logp nor rollout_logp), grpo_loss_is (rollout_logp, cap, level) or grpo_loss_clip (old_logp, eps_low, eps_high, w)
+    with a row normaliser and an optional reference.  row_scale 0: every row's sums are divided by its live tokens (those three calls); > 0: multiplied by this
+    factor instead (row_kl keeps its row mean).  ref_logp None (needs beta == 0): no KL term, kl and row_kl come back as zeros.  Returns the tuple of the call it
+    generalises: (dlogp, kl, row_loss, row_kl), + (w [N, C], row_stats [N, 5]) with rollout_logp, + (row_stats [N, 4],) with old_logp."""
+    if level not in IS_LEVELS:
+        raise ValueError(f"grpo_loss_ex: level must be one of {sorted(IS_LEVELS)}, got {level!r}")
+    N, C = logp.shape
+    dev = logp.device
+    dlogp = torch.empty(N, C, dtype=F32, device=dev)
+    kl = torch.empty(N, C, dtype=F32, device=dev)
+    row_loss = torch.empty(N, dtype=F32, device=dev)
+    row_kl = torch.empty(N, dtype=F32, device=dev)
+    w_out = torch.empty(N, C, dtype=F32, device=dev) if (rollout_logp is not None and old_logp is None) else None
+    stats = torch.empty(N, 4 if old_logp is not None else 5, dtype=F32, device=dev) if (old_logp is not None or rollout_logp is not None) else None
+    hip.call("grpo_loss_ex", logp, ref_logp, old_logp, rollout_logp, w, adv, mask, float(beta), float(cap), IS_LEVELS[level], float(eps_low), float(eps_high),
+             float(row_scale), int(n_total_rows or N), dlogp, kl, row_loss, row_kl, w_out, stats, N, C)
+    if old_logp is not None:
+        return dlogp, kl, row_loss, row_kl, stats
+    if rollout_logp is not None:
+        return dlogp, kl, row_loss, row_kl, w_out, stats
+    return dlogp, kl, row_loss, row_kl
+
+
 _sample_ws = {}
 
 

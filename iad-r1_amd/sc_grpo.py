@@ -60,6 +60,15 @@ class GRPOArgs:
     num_iterations: int = 1
     epsilon: float = 0.2
     epsilon_high: float | None = None
+    # how a step's per-token terms are normalised (REF trl/trl/trainer/grpo_trainer.py:1212-1219): "grpo" = every row a mean over its own live tokens, then the mean
+    # over rows; "bnpo" = the sum over the step's rows divided by their live tokens; "dr_grpo" = divided by rows x max_completion_length.  The default is "grpo", not
+    # trl's "bnpo": that is what the reference's trainer computes (sc_grpo_trainer.py:796-798).  Anything but "grpo" goes through iadr1_grpo_loss_ex.
+    loss_type: str = "grpo"
+    # False: advantages = reward - group mean, not divided by the group's std + 1e-4 (REF ...grpo_trainer.py:1080-1082); reward_std is logged either way
+    scale_rewards: bool = True
+    # a completion that reached max_completion_length without an EOS drops out of the loss: its row of the loss mask is zeroed (REF ...grpo_trainer.py:983-986), and
+    # the step logs completions/clipped_ratio, the share of such rows (REF ...grpo_trainer.py:1105)
+    mask_truncated_completions: bool = False
     learning_rate: float = 1e-6
     weight_decay: float = 0.0
     adam_beta1: float = 0.9
@@ -103,12 +112,42 @@ def check_reuse_args(who: str, num_iterations, epsilon, epsilon_high):
         raise ValueError(f"{who}.epsilon_high must be None (= epsilon) or finite and >= 0 (got {epsilon_high})")
 
 
+LOSS_TYPES = ("grpo", "bnpo", "dr_grpo")
+
+
+def check_objective_args(who: str, loss_type, mask_truncated_completions=False, suppress_eos=False):
+    """loss_type / mask_truncated_completions of GRPOArgs and GRPOConfig (`who` names the class in the message)."""
+    if loss_type not in LOSS_TYPES:
+        raise ValueError(f"{who}.loss_type must be one of {list(LOSS_TYPES)} (got {loss_type!r})")
+    if mask_truncated_completions and suppress_eos:
+        raise ValueError(f"{who}.mask_truncated_completions with suppress_eos: no completion can end in an EOS, so every row would be masked and the step would have no loss")
+
+
 def eos_completion_mask(completion_ids: np.ndarray, eos_token_id: int) -> np.ndarray:
     """REF:722-726 -- keep tokens up to and including the first EOS."""
     is_eos = completion_ids == eos_token_id
     n, c = is_eos.shape
     eos_idx = np.where(is_eos.any(1), is_eos.argmax(1), c)
     return (np.arange(c)[None, :] <= eos_idx[:, None]).astype(np.int32)
+
+
+def truncation_loss_mask(cmask: np.ndarray, completion_ids: np.ndarray, eos_token_id: int) -> np.ndarray:
+    """REF trl/trl/trainer/grpo_trainer.py:983-986 -- the EOS mask with the rows that hold no EOS zeroed."""
+    has_eos = (np.asarray(completion_ids) == eos_token_id).any(1)
+    return cmask * has_eos[:, None].astype(cmask.dtype)
+
+
+def loss_row_scale(loss_type: str, loss_mask: np.ndarray, max_completion_length: int) -> float:
+    """The row_scale of iadr1_grpo_loss_ex for one step's [N, C] loss mask, so that the mean of its row_loss over the N rows is trl's loss (REF
+    trl/trl/trainer/grpo_trainer.py:1213 / 1215 / 1217): 0 for "grpo" (the kernel divides every row by its own live tokens), N / max(live tokens, 1) for "bnpo",
+    1 / max_completion_length for "dr_grpo".  Computed in float64 and rounded once to the float32 the kernel takes."""
+    if loss_type == "grpo":
+        return 0.0
+    if loss_type == "bnpo":
+        return float(np.float32(np.float64(loss_mask.shape[0]) / np.float64(max(int(np.asarray(loss_mask, dtype=np.int64).sum()), 1))))
+    if loss_type == "dr_grpo":
+        return float(np.float32(np.float64(1.0) / np.float64(max_completion_length)))
+    raise ValueError(f"loss_type must be one of {list(LOSS_TYPES)} (got {loss_type!r})")
 
 
 def pad(rows, padding_value=0, padding_side: str = "right", pad_to_multiple_of: int | None = None) -> np.ndarray:
@@ -150,11 +189,14 @@ def right_padding_shift(row_ids: np.ndarray, pad_token_id: int) -> int:
     return int(len(row_ids) - first) if bool((row_ids[first:] == pad_token_id).all()) else 0
 
 
-def group_advantages(rewards: torch.Tensor, G: int):
-    """REF:787-793: group mean, UNBIASED std, eps 1e-4."""
+def group_advantages(rewards: torch.Tensor, G: int, scale: bool = True):
+    """REF:787-793: group mean, UNBIASED std, eps 1e-4.  scale False (REF trl/trl/trainer/grpo_trainer.py:1080-1082 with scale_rewards off): rewards - group mean;
+    the std is returned either way."""
     r = rewards.view(-1, G)
     mean = r.mean(1).repeat_interleave(G)
     std = r.std(1).repeat_interleave(G) if G > 1 else torch.zeros_like(mean)
+    if not scale:
+        return rewards - mean, std
     return (rewards - mean) / (std + 1e-4), std
 
 
@@ -344,7 +386,9 @@ class _nullcontext:
 
 
 class SCGRPOEngine:
-    def __init__(self, cfg: VLMConfig, policy: ParamStore, ref: ParamStore, args: GRPOArgs, group=None):
+    def __init__(self, cfg: VLMConfig, policy: ParamStore, ref: ParamStore | None, args: GRPOArgs, group=None):
+        """ref: the frozen reference's store, or None with args.beta == 0 (REF trl/trl/trainer/grpo_trainer.py:407): the step then has no KL term, runs no reference
+        pass of any kind (also when a store is given) and takes the sequential structure -- see _shadow_cus."""
         if args.top_k <= 0 and args.top_p != 1.0:
             raise ValueError(f"GRPOArgs.top_k <= 0 samples the whole vocabulary and needs top_p == 1.0 (got top_p = {args.top_p}): a nucleus over all tokens is not built")
         if args.rollout_is_cap != 0 and not (math.isfinite(args.rollout_is_cap) and args.rollout_is_cap >= 1.0):
@@ -355,12 +399,17 @@ class SCGRPOEngine:
             raise ValueError("GRPOArgs.rollout_is_cap with llava_rotate_right_padded_rows: that path scores a rotated window, whose columns do not line up with the "
                              "rollout's log-probs; set llava_rotate_right_padded_rows=False to weight the completion tokens themselves")
         check_reuse_args("GRPOArgs", args.num_iterations, args.epsilon, args.epsilon_high)
+        check_objective_args("GRPOArgs", args.loss_type, args.mask_truncated_completions, args.suppress_eos)
+        if ref is None and args.beta != 0:
+            raise ValueError(f"GRPOArgs.beta = {args.beta} needs the frozen reference's ParamStore (ref=None is legal only with beta == 0: the KL term reads its log-probs)")
         self.cfg, self.args = cfg, args
+        if args.beta == 0:
+            self._shadow_cus(0)         # a forced IADR1_OVERLAP_CUS is refused here already, not at the first rollout
         self.last_rollout_logps = None      # [N, C] device tensor of the last rollout when args.wants_rollout_logps
-        self.pol, self.ref = Engine(policy), Engine(ref)
+        self.pol, self.ref = Engine(policy), (Engine(ref) if ref is not None else None)
         self.dev = policy.device
         self.reducer = GradReducer(policy, group)
-        self.pol.resident_extra = ref.resident_bytes() + self.reducer.staging_bytes()       # static inputs of Engine.recompute_wanted("auto")
+        self.pol.resident_extra = (ref.resident_bytes() if ref is not None else 0) + self.reducer.staging_bytes()       # static inputs of Engine.recompute_wanted("auto")
         self.opt_step = 0
         self.accum = 0
         self._rollout = None
@@ -450,8 +499,8 @@ class SCGRPOEngine:
         others -- two CU-masked streams (include/iadr1_hip.h iadr1_stream_create_cu_mask) on different dispatch pipes (overlap.cu_split, one pair per process); the
         decode launchers size their persistent grids for the smaller device (iadr1_set_decode_cus).  Masked streams are BLOCKING streams: `step` moves off the null
         stream while they are in use."""
-        from .overlap import cu_split, shadow_cus
-        n = shadow_cus(self.cfg, N, self.args.max_completion_length)
+        from .overlap import cu_split
+        n = self._shadow_cus(N)
         self._shadow_stream = None
         if n <= 0 or self.dev.type != "cuda" or not ChunkedRefPass.applicable(self.cfg, N, self.args.max_completion_length):
             return {}
@@ -472,6 +521,19 @@ class SCGRPOEngine:
             return {}
         self._shadow_stream = sp[1]
         return {"decode_cus": sp[2], "decode_stream": sp[0]}
+
+    def _shadow_cus(self, N: int) -> int:
+        """overlap.shadow_cus for this engine.  With beta == 0 there is no reference pass to put under the rollout, so the step is the sequential one and the decode
+        grids keep the whole device: `auto` resolves to 0, and a forced split is refused (a run that asked for one step structure must not silently get the other)."""
+        from .overlap import shadow_cus
+        if self.args.beta != 0:
+            return shadow_cus(self.cfg, N, self.args.max_completion_length)
+        v = os.environ.get("IADR1_OVERLAP_CUS", "auto").strip().lower()
+        if v not in ("", "auto", "0"):      # every forced side stream, -1 (the ordinary second stream) included, and anything that is not a number
+            raise ValueError(f"IADR1_OVERLAP_CUS={v} with GRPOArgs.beta == 0: the co-scheduled step puts the frozen reference's pass under the rollout (n > 0: on a CU share, "
+                             "-1: on an ordinary second stream), and a step without a KL term runs no reference pass; unset it (auto: the sequential step, decode on the whole "
+                             "device) or set it to 0")
+        return 0
 
     def _rollout_fuses_swiglu(self, N) -> bool:
         """True when the decode gate|up projection runs on the persistent fused-SwiGLU kernel (the one with side outputs): include/iadr1_hip.h."""
@@ -496,7 +558,10 @@ class SCGRPOEngine:
         loss is then the clipped surrogate against them (iadr1_grpo_loss_clip with args.epsilon / epsilon_high), the rollout/* metrics are not produced, and the
         metrics gain clip_ratio/low_mean, clip_ratio/high_mean, clip_ratio/region_mean (shares of this call's live tokens), policy/ratio_mean and
         policy/logp_abs_diff_max; result "old_logps".  With args.rollout_is_cap > 0 it needs is_weights, the "rollout_is_weights" of that earlier call: the weight of
-        the sampling engine against the policy that sampled does not change while its rollout is reused."""
+        the sampling engine against the policy that sampled does not change while its rollout is reused.
+        args.beta == 0: no reference pass runs and ref_logps is not read; results "ref_logps" and "kl" are None and the metrics have no "kl".  args.loss_type other
+        than "grpo" changes the row normaliser (loss_row_scale); args.mask_truncated_completions zeroes the loss-mask rows without an EOS (result "completion_mask",
+        metric completions/clipped_ratio).  Either of the first two sends the call through iadr1_grpo_loss_ex."""
         a, c = self.args, self.cfg
         use_clip = old_logps is not None
         use_is = a.rollout_is_cap > 0 and not use_clip
@@ -522,10 +587,17 @@ class SCGRPOEngine:
                                      f"sampled these completions: got {None if is_weights is None else tuple(is_weights.shape)}")
                 w_clip = is_weights.to(F32)
         cmask = eos_completion_mask(comp, c.eos_token_id)
+        # the loss mask: what the loss kernel, the row_scale and clip / IS metric denominators and the returned "completion_mask" see.  The text plans, the llava
+        # rotation and completion_length keep the EOS mask (trl also zeroes the attention mask of a dropped row; the live rows do not attend to it either way)
+        lmask = truncation_loss_mask(cmask, comp, c.eos_token_id) if a.mask_truncated_completions else cmask
+        no_ref = a.beta == 0            # no KL term: no reference pass, nothing read through a reference pointer
+        use_ex = no_ref or a.loss_type != "grpo"
+        # one value per call, from all N rows of the host-resident mask (not per micro-batch: results keep not depending on micro_batch_seqs)
+        row_scale = loss_row_scale(a.loss_type, lmask, a.max_completion_length)
         ids = np.concatenate([np.repeat(ids_p, G, 0), comp], 1)
         mask = np.concatenate([np.repeat(mask_p, G, 0), cmask.astype(mask_p.dtype)], 1)
         S = P + C
-        cmask_d = ops.h2d(cmask, self.dev)
+        cmask_d = ops.h2d(lmask, self.dev)
         state = {}
 
         def advantages():
@@ -534,7 +606,7 @@ class SCGRPOEngine:
             if not state:
                 rpf = rewards_per_func() if callable(rewards_per_func) else rewards_per_func
                 rpf = torch.as_tensor(np.asarray(rpf), dtype=F32)
-                adv, std = group_advantages(rpf.sum(1), G)
+                adv, std = group_advantages(rpf.sum(1), G, a.scale_rewards)
                 # pinned + non-blocking: a pageable host-to-device copy synchronises the stream, i.e. would make the host wait here for the reference and policy
                 # forwards it has just enqueued (and leave the GPU idle for the ~1 ms the host then needs to launch the loss kernel)
                 state.update(rpf=rpf, rewards=rpf.sum(1), adv=adv, std=std, adv_d=ops.h2d(adv, self.dev))
@@ -543,15 +615,15 @@ class SCGRPOEngine:
         if vis is None or (backward and vis["ctx"] is None):
             vis = self.vision_policy(batch, save=backward)
         grids, plan_v, px, rows, img_pol, vctx = vis["grids"], vis["plan"], vis["px"], vis["rows"], vis["img"], vis["ctx"]
-        have_ref = ref_logps is not None and tuple(ref_logps.shape) == (N, C)
+        have_ref = not no_ref and ref_logps is not None and tuple(ref_logps.shape) == (N, C)
         shadowed = have_ref and ref_logps is self.shadow_logps      # this step's rollout ran the shadow pass that wrote them (else: handed in by the caller, nothing to join)
-        img_ref = None if have_ref else self.ref.vision_forward(px, plan_v, save=False)[0]
+        img_ref = None if (have_ref or no_ref) else self.ref.vision_forward(px, plan_v, save=False)[0]
         gpr, off = self._per_row_images(batch, grids, rows)
         dimg32 = torch.zeros(img_pol.shape, dtype=F32, device=self.dev) if backward else None
 
         logp_all = torch.empty(N, C, dtype=F32, device=self.dev)
-        ref_all = torch.empty(N, C, dtype=F32, device=self.dev)
-        kl_all = torch.empty(N, C, dtype=F32, device=self.dev)
+        ref_all = None if no_ref else torch.empty(N, C, dtype=F32, device=self.dev)
+        kl_all = None if no_ref else torch.empty(N, C, dtype=F32, device=self.dev)
         row_loss = torch.empty(N, dtype=F32, device=self.dev)
         row_kl = torch.empty(N, dtype=F32, device=self.dev)
         if use_is:
@@ -604,7 +676,8 @@ class SCGRPOEngine:
                 sel = sel.reshape(-1)
             rows_d = ops.h2d(sel.astype(np.int64), self.dev)
             tgt_d = ops.h2d(tgt.reshape(-1), self.dev)
-            if not have_ref:
+            rl = None
+            if not have_ref and not no_ref:
                 hf, _ = self.ref.text_forward(plan, img_ref, save=False)
                 rl, _ = self.ref.logprobs(hf, rows_d, tgt_d, save=False)
                 del hf
@@ -629,7 +702,21 @@ class SCGRPOEngine:
                 if si == 0 and shadowed:
                     self._shadow.join()          # the tail chunk of the shadow pass ran next to the policy's lm_head; everything after this reads its log-probs
                 rl = ref_logps[r0:r1].contiguous()
-            if use_clip:
+            if use_ex:
+                # beta == 0 or another loss_type than "grpo": the same three forms through iadr1_grpo_loss_ex
+                form = {}
+                if use_clip:
+                    form = dict(old_logp=old_all[r0:r1].contiguous(), w=None if w_clip is None else w_clip[r0:r1].contiguous(), eps_low=a.epsilon, eps_high=eps_high)
+                elif use_is:
+                    form = dict(rollout_logp=ro_all[r0:r1].contiguous(), cap=a.rollout_is_cap, level=a.rollout_is_level)
+                res = ops.grpo_loss_ex(lp.view(n, C), adv_d[r0:r1].contiguous(), cmask_d[r0:r1].contiguous(), a.beta, ref_logp=None if no_ref else rl.view(n, C),
+                                       row_scale=row_scale, n_total_rows=N, **form)
+                dlogp, kl, rloss, rkl = res[:4]
+                if use_clip:
+                    clip_stats[r0:r1] = res[4]
+                elif use_is:
+                    w_all[r0:r1], is_stats[r0:r1] = res[4], res[5]
+            elif use_clip:
                 dlogp, kl, rloss, rkl, clip_stats[r0:r1] = ops.grpo_loss_clip(lp.view(n, C), old_all[r0:r1].contiguous(), rl.view(n, C), adv_d[r0:r1].contiguous(),
                                                                               cmask_d[r0:r1].contiguous(), a.beta, a.epsilon, eps_high,
                                                                               w=None if w_clip is None else w_clip[r0:r1].contiguous(), n_total_rows=N)
@@ -638,7 +725,9 @@ class SCGRPOEngine:
                                                                                       cmask_d[r0:r1].contiguous(), a.beta, a.rollout_is_cap, a.rollout_is_level, n_total_rows=N)
             else:
                 dlogp, kl, rloss, rkl = ops.grpo_loss(lp.view(n, C), rl.view(n, C), adv_d[r0:r1].contiguous(), cmask_d[r0:r1].contiguous(), a.beta, n_total_rows=N)
-            logp_all[r0:r1], ref_all[r0:r1], kl_all[r0:r1] = lp.view(n, C), rl.view(n, C), kl
+            logp_all[r0:r1] = lp.view(n, C)
+            if not no_ref:
+                ref_all[r0:r1], kl_all[r0:r1] = rl.view(n, C), kl
             row_loss[r0:r1], row_kl[r0:r1] = rloss, rkl
             if backward:
                 dhf = self.pol.logprobs_backward(dlogp.view(-1), lctx)
@@ -652,24 +741,26 @@ class SCGRPOEngine:
             self.accum += 1
         st = advantages()
         metrics = {"completion_length": float(cmask.sum(1).mean()), "reward": float(st["rewards"].mean()), "reward_std": float(st["std"].mean())}
+        if a.mask_truncated_completions:
+            metrics["completions/clipped_ratio"] = 1.0 - float((comp == c.eos_token_id).any(1).mean())        # REF trl/trl/trainer/grpo_trainer.py:1103-1106
         means = [row_loss.mean(), row_kl.mean()]
         ro_lp = None
         if use_clip:
             # clipped shares, mean ratio and largest |logp - old_logp| over this call's live tokens, from the loss kernel's per-row partials
-            cnt = float(max(1, int(cmask.sum())))
+            cnt = float(max(1, int(lmask.sum())))
             sums = clip_stats.sum(0) / cnt
             means += [sums[0], sums[1], sums[2], clip_stats[:, 3].max()]
         elif use_is:
             # the same three rollout/* means from the loss kernel's per-row partials (columns: include/iadr1_hip.h), plus the mean weight and the clipped share
             ro_lp = ro_all
-            cnt = float(max(1, int(cmask.sum())))
+            cnt = float(max(1, int(lmask.sum())))
             sums = is_stats.sum(0) / cnt
             means += [sums[2], is_stats[:, 3].max(), sums[4], sums[0], sums[1]]
         elif rollout_logps is not None and not use_clip:
             # sampled (the rollout's logits) vs scored (the policy forward of the loss) log-probs of the same tokens, over the completion mask; k3 estimator of
             # KL(sampled || scored) in the form iadr1_grpo_loss uses for policy vs reference: exp(d) - d - 1 with d = scored - sampled
             ro_lp = rollout_logps[:, :C].to(F32)
-            m_ = cmask_d.to(F32)
+            m_ = (cmask_d if lmask is cmask else ops.h2d(cmask, self.dev)).to(F32)      # a diagnostic of the rollout, not of the loss: the EOS mask
             d_ = (logp_all - ro_lp) * m_
             cnt = m_.sum().clamp(min=1.0)
             means += [d_.abs().sum() / cnt, d_.abs().max(), ((torch.exp(d_) - d_ - 1.0) * m_).sum() / cnt]
@@ -677,7 +768,9 @@ class SCGRPOEngine:
 
         def finalize():
             lk = dev_means.tolist()
-            metrics.update(loss=lk[0], kl=lk[1])
+            metrics.update(loss=lk[0])
+            if not no_ref:          # as in trl (REF trl/trl/trainer/grpo_trainer.py:1224): no kl key without a KL term
+                metrics.update(kl=lk[1])
             if use_clip:
                 metrics.update({"clip_ratio/low_mean": lk[2], "clip_ratio/high_mean": lk[3], "clip_ratio/region_mean": lk[2] + lk[3], "policy/ratio_mean": lk[4],
                                 "policy/logp_abs_diff_max": lk[5]})
@@ -690,7 +783,7 @@ class SCGRPOEngine:
             metrics["finalize"] = finalize
         else:
             finalize()
-        out = {"metrics": metrics, "logps": logp_all, "ref_logps": ref_all, "kl": kl_all, "advantages": st["adv"], "completion_mask": cmask,
+        out = {"metrics": metrics, "logps": logp_all, "ref_logps": ref_all, "kl": kl_all, "advantages": st["adv"], "completion_mask": lmask,
                "rewards_per_func": st["rpf"], "ids": ids, "mask": mask}
         if ro_lp is not None:
             out["rollout_logps"] = ro_lp
@@ -743,12 +836,11 @@ class SCGRPOEngine:
         return self._step(*args, **kw)
 
     def _splits_cus(self, batch) -> bool:
-        from .overlap import shadow_cus
         try:
             n_seq = len(batch["input_ids"]) * self.args.num_generations
         except Exception:
             return False
-        return shadow_cus(self.cfg, n_seq, self.args.max_completion_length) > 0
+        return self._shadow_cus(n_seq) > 0
 
     def _step(self, batch, reward_fn, do_optimizer_step=True, last_micro_step=None, return_outputs=False, defer_metrics=False, completions=None, rollout_logps=None,
               ref_logps=None, old_logps=None, is_weights=None):
@@ -790,7 +882,7 @@ class SCGRPOEngine:
             P_ = np.asarray(batch["input_ids"]).shape[1] if a.max_prompt_length is None else min(np.asarray(batch["input_ids"]).shape[1], a.max_prompt_length)
             if self.pol.recompute_wanted(len(batch["input_ids"]) * P_ + N * a.max_completion_length, a.recompute):
                 carry = None       # gradient checkpointing: nothing of the rollout is kept, the policy forward runs (checkpointed) before backward
-        comp = self.rollout(batch, vis=vis, train_carry=carry, shadow_ref=True) if completions is None else np.asarray(completions)
+        comp = self.rollout(batch, vis=vis, train_carry=carry, shadow_ref=a.beta != 0) if completions is None else np.asarray(completions)
         ref_lp = self.shadow_logps if completions is None else ref_logps
         pol_head = self.shadow_policy_head if completions is None else None
         ro_lp = (self.last_rollout_logps if completions is None else rollout_logps) if self.args.wants_rollout_logps else None

@@ -25,7 +25,7 @@ import torch
 
 from . import schedule
 from .params import ParamStore, VLMConfig
-from .sc_grpo import GRPOArgs, SCGRPOEngine, check_reuse_args
+from .sc_grpo import GRPOArgs, SCGRPOEngine, check_objective_args, check_reuse_args
 
 
 @dataclass
@@ -52,6 +52,12 @@ class GRPOConfig:
     num_iterations: int = 1
     epsilon: float = 0.2
     epsilon_high: Optional[float] = None    # None: epsilon
+    # trl.GRPOConfig's names (GRPOArgs has the details).  loss_type: "grpo" | "bnpo" | "dr_grpo" -- the default is "grpo", what the reference's trainer computes, not
+    # trl's "bnpo".  scale_rewards False: advantages are not divided by the group's std.  mask_truncated_completions: completions without an EOS leave the loss.
+    # beta 0 builds no frozen reference at all (self.ref is None): no copy of the weights, no reference pass, no kl metric.
+    loss_type: str = "grpo"
+    scale_rewards: bool = True
+    mask_truncated_completions: bool = False
     learning_rate: float = 1e-6
     weight_decay: float = 0.0
     adam_beta1: float = 0.9
@@ -336,6 +342,7 @@ class SCGRPOTrainer:
             args = GRPOConfig(output_dir=f"{os.path.basename(name.rstrip('/'))}-GRPO")
         self.args = args
         check_reuse_args("GRPOConfig", args.num_iterations, args.epsilon, args.epsilon_high)
+        check_objective_args("GRPOConfig", args.loss_type)
         if args.save_steps and args.save_steps % args.num_iterations != 0:
             raise ValueError(f"GRPOConfig.save_steps ({args.save_steps}) must be a multiple of num_iterations ({args.num_iterations}): a checkpoint holds no cached "
                              "rollout, so a run can only continue from the first optimizer step of a generation")
@@ -376,9 +383,11 @@ class SCGRPOTrainer:
             else:
                 self.policy = ParamStore(self.cfg, self.device, trainable=True)
                 self.policy.load_named(weights)
-        # frozen reference = the starting checkpoint (REF:152-182)
-        self.ref = ParamStore(self.cfg, self.device, trainable=False)
-        self.ref.copy_from(self.policy)
+        # frozen reference = the starting checkpoint (REF:152-182); none without a KL term (REF trl/trl/trainer/grpo_trainer.py:407)
+        self.ref = None
+        if args.beta != 0:
+            self.ref = ParamStore(self.cfg, self.device, trainable=False)
+            self.ref.copy_from(self.policy)
         if processing_class is None:
             if not isinstance(model, str):
                 raise ValueError("processing_class is required when the model is passed in memory")
@@ -400,7 +409,8 @@ class SCGRPOTrainer:
         self.engine = SCGRPOEngine(self.cfg, self.policy, self.ref, GRPOArgs(
             num_generations=args.num_generations, max_prompt_length=args.max_prompt_length, max_completion_length=args.max_completion_length,
             beta=args.beta, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, rollout_logps=args.rollout_logps, rollout_is_cap=args.rollout_is_cap, rollout_is_level=args.rollout_is_level,
-            num_iterations=args.num_iterations, epsilon=args.epsilon, epsilon_high=args.epsilon_high, learning_rate=args.learning_rate, weight_decay=args.weight_decay,
+            num_iterations=args.num_iterations, epsilon=args.epsilon, epsilon_high=args.epsilon_high, loss_type=args.loss_type, scale_rewards=args.scale_rewards,
+            mask_truncated_completions=args.mask_truncated_completions, learning_rate=args.learning_rate, weight_decay=args.weight_decay,
             adam_beta1=args.adam_beta1, adam_beta2=args.adam_beta2, adam_epsilon=args.adam_epsilon, max_grad_norm=args.max_grad_norm,
             gradient_accumulation_steps=args.gradient_accumulation_steps, micro_batch_seqs=args.micro_batch_seqs, seed=args.seed,
             # under data parallelism the policy is "auto" even without the flag: it recomputes only where the static budget (which then reserves RCCL's buffers) is tight
@@ -497,9 +507,11 @@ class SCGRPOTrainer:
             comp = out["completion_ids"] if self.cfg.is_llava else trim_completions(out["completion_ids"], self.cfg.eos_token_id)
             c = comp.shape[1]
             w = out.get("rollout_is_weights")
-            self._generation.append({"batch": batch, "completions": comp, "old_logps": out["logps"][:, :c].contiguous(), "ref_logps": out["ref_logps"][:, :c].contiguous(),
+            self._generation.append({"batch": batch, "completions": comp, "old_logps": out["logps"][:, :c].contiguous(), "ref_logps": None if out["ref_logps"] is None else out["ref_logps"][:, :c].contiguous(),
                                      "rewards_per_func": out["rewards_per_func"], "is_weights": None if w is None else w[:, :c].contiguous()})
         self._metrics["completion_length"].append(m["completion_length"])
+        if "completions/clipped_ratio" in m:        # (mask_truncated_completions: a job-wide option, so every rank logs the same keys)
+            self._metrics["completions/clipped_ratio"].append(m["completions/clipped_ratio"])
         rp = out["rewards_per_func"].mean(0)
         for i, f in enumerate(self.reward_funcs):
             self._metrics[f"rewards/{reward_func_name(f)}"].append(float(rp[i]))
@@ -511,7 +523,8 @@ class SCGRPOTrainer:
         def finish():
             if "finalize" in m:
                 m.pop("finalize")()
-            self._metrics["kl"].append(m["kl"])
+            if "kl" in m:       # absent with beta == 0, on every rank alike
+                self._metrics["kl"].append(m["kl"])
             for k in ("rollout/logp_abs_diff_mean", "rollout/logp_abs_diff_max", "rollout/kl", "rollout/is_weight_mean", "rollout/is_clipped_frac",
                       "clip_ratio/low_mean", "clip_ratio/high_mean", "clip_ratio/region_mean", "policy/ratio_mean", "policy/logp_abs_diff_max"):
                 if k in m:

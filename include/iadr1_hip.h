@@ -310,6 +310,26 @@ int iadr1_grpo_loss_is(const float* logp, const float* ref_logp, const float* ro
 int iadr1_grpo_loss_clip(const float* logp, const float* old_logp, const float* ref_logp, const float* adv, const int* mask, const float* w /* may be NULL */,
                          float beta, float eps_low, float eps_high, int n_total_rows, float* dlogp, float* kl, float* row_loss, float* row_kl,
                          float* row_stats /* [N,4] */, int N, int C, iadr1_stream_t stream);
+/* grpo_loss_ex: the three calls above behind one entry point, with the two things trl's GRPOTrainer has and they lack: the row normaliser of its `loss_type`
+ * (REF:trl/trl/trainer/grpo_trainer.py:1212-1219) and a step without a reference model (beta == 0: REF:...grpo_trainer.py:407, 1004-1005, 1193, 1209, 1224).
+ * Which form runs follows from the optional inputs: old_logp -> the clipped surrogate of iadr1_grpo_loss_clip (REF:1203-1210; w as there), rollout_logp -> the
+ * truncated importance weight of iadr1_grpo_loss_is (cap, level, w_out), neither -> iadr1_grpo_loss (REF:1192-1202 with exp(p - sg p) = 1).  t_i is that form's
+ * per-token term, g_i its derivative and w_i its weight (1 where the form has none), all exactly as in those calls.  Over the mask m, cnt = sum_i m_i:
+ *   s = row_scale > 0 ? row_scale : (cnt > 0 ? 1 / cnt : 0)
+ *   row_loss = s * sum_i m_i w_i t_i,   dlogp_i = m_i * s / n_total_rows * w_i * g_i,   row_kl = sum_i m_i kl_i / cnt  whatever row_scale is
+ * so that mean(row_loss) over the N = n_total_rows rows of a step is trl's loss for
+ *   row_scale 0 ("grpo", REF:1213: every row a mean over its own live tokens),   row_scale N / max(live tokens of the batch, 1) ("bnpo", REF:1215),
+ *   row_scale 1 / max_completion_length ("dr_grpo", REF:1217).
+ * The sequence-level importance ratio keeps its row mean over cnt.  ref_logp NULL (needs beta == 0): no reference log-prob is read, kl_i = 0, kl (if given)
+ * and row_kl are written as 0 and the gradient is the advantage term alone -- on finite inputs dlogp and row_loss equal those of a call with any ref_logp at
+ * beta == 0.  With ref_logp given and row_scale == 0 every output is bit-equal to the matching call above.  kl, w_out may be NULL; row_stats: [N, 5] (IS form),
+ * [N, 4] (clipped form), unused (may be NULL) otherwise.  One block per row, fixed-order block reductions, no float atomics: run-to-run bit-identical.
+ * Refused on the host: ref_logp NULL with beta != 0; row_scale negative or not finite; old_logp together with rollout_logp; w without old_logp; row_stats NULL
+ * where the form writes it; cap / level (IS form) and eps_low / eps_high (clipped form) as in those calls; N <= 0, C <= 0, n_total_rows < N. */
+int iadr1_grpo_loss_ex(const float* logp, const float* ref_logp /* may be NULL */, const float* old_logp /* may be NULL */, const float* rollout_logp /* may be NULL */,
+                       const float* w /* may be NULL */, const float* adv, const int* mask, float beta, float cap, int level, float eps_low, float eps_high,
+                       float row_scale, int n_total_rows, float* dlogp, float* kl /* may be NULL */, float* row_loss, float* row_kl, float* w_out /* may be NULL */,
+                       float* row_stats, int N, int C, iadr1_stream_t stream);
 
 /* ---- optimizer (HF Trainer default AdamW + clip_grad_norm_, TF:trainer.py:1168) ------------------------------- */
 /* out[0] = sum(g^2), deterministic (fixed-order two-stage reduction; scratch = 2048 floats) so that data-parallel

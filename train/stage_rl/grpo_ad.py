@@ -77,7 +77,7 @@ def build_parser():
     p.add_argument("--num_generations", type=int, default=8)
     p.add_argument("--max_prompt_length", type=int, default=512)
     p.add_argument("--max_completion_length", type=int, default=256)
-    p.add_argument("--beta", type=float, default=0.04)
+    p.add_argument("--beta", type=float, default=0.04, help="KL coefficient; 0: no KL term, and no frozen reference model is built or run")
     p.add_argument("--temperature", type=float, default=0.9)
     p.add_argument("--top_k", type=int, default=50, help="rollout sampler (the reference hard-codes 50); <= 0: the whole vocabulary, needs --top_p 1.0")
     p.add_argument("--top_p", type=float, default=0.9)
@@ -91,6 +91,12 @@ def build_parser():
                    help="optimizer steps per rollout (trl's mu): steps after the first of a generation score the same completions again under the clipped surrogate")
     p.add_argument("--epsilon", type=float, default=0.2, help="lower clip bound 1 - epsilon of the policy ratio (and the upper one unless --epsilon_high); read when --num_iterations > 1")
     p.add_argument("--epsilon_high", type=float, default=None, help="upper clip bound 1 + epsilon_high; default: --epsilon")
+    p.add_argument("--loss_type", default="grpo", choices=["grpo", "bnpo", "dr_grpo"],
+                   help="normaliser of the per-token loss terms: per completion (grpo, the reference's), per live token of the step (bnpo), or max_completion_length (dr_grpo)")
+    p.add_argument("--scale_rewards", nargs="?", default=True, const=True, type=lambda v: str(v).lower() in ("1", "true", "yes"),
+                   help="false: advantages are reward - group mean, not divided by the group's std")
+    p.add_argument("--mask_truncated_completions", nargs="?", default=False, const=True, type=lambda v: str(v).lower() in ("1", "true", "yes"),
+                   help="completions that reach --max_completion_length without an EOS leave the loss; logs completions/clipped_ratio")
     p.add_argument("--learning_rate", type=float, default=1e-6)
     p.add_argument("--weight_decay", type=float, default=0.0)
     p.add_argument("--max_grad_norm", type=float, default=1.0)

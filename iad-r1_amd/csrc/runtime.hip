@@ -83,6 +83,7 @@ extern "C" int iadr1_stream_destroy(void* stream) {
 }
 
 extern "C" const char* iadr1_last_error(void) { return g_err; }
+// 115: iadr1_sample_ex / iadr1_sample_ex_workspace_bytes (repetition penalty over a per-sequence seen bitmap, min_p) and iadr1_seen_init; nothing else changed
 // 111: iadr1_sample_logp / iadr1_sample_logp_workspace_bytes (whole-vocabulary sampling for top_k <= 0, log-prob of the sampled token); nothing else changed
 // 110: the weight prefetcher (iadr1_weight_prefetch) and the three progress-mark fields at the end of iadr1_side_out_t are gone
 // 109: round 6 -- iadr1_weight_prefetch (persistent memory-side-cache prefetcher of the rollout, paced by iadr1_side_out_t.mark: three new fields at the END of the struct)
@@ -91,5 +92,5 @@ extern "C" const char* iadr1_last_error(void) { return g_err; }
 // 106: round 5 -- CU-masked streams, decode CU count, iadr1_attn_fwd_chunk, iadr1_wait_counter (co-scheduled rollout / teacher-forced forward); ordered two-stage
 //      gradient reductions: workspace arguments on iadr1_rmsnorm_bwd / iadr1_layernorm_bwd / iadr1_colsum_acc, iadr1_rows_scatter_acc replaces iadr1_embed_bwd
 // 104: round 4 -- iadr1_decode_advance gained the all_done / rotary-table arguments, the FP8-MFMA pair (iadr1_quant_rows_fp8, iadr1_gemm_nt_fp8) is gone
-extern "C" int iadr1_version(void) { return 114; }
+extern "C" int iadr1_version(void) { return 115; }
 

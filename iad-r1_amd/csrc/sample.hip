@@ -165,7 +165,9 @@ __device__ __forceinline__ int eff_k(const SampleArgs& p) {
 
 // The single-thread tail of stage 2: softmax over the n rank-sorted candidates in sval (weights left in w), top-p cut, inverse-CDF draw.  Returns the
 // RANK of the pick.  One function for both stage-2 kernels: iadr1_sample_logp's ids are bit-equal to iadr1_sample_topk_topp's because they are this code.
-__device__ __forceinline__ int topk_topp_pick(const SampleArgs& p, int row, const float* sval, float* w, int n) {
+// min_p (iadr1_sample_ex; 0 from the two older entry points, where the compare folds away): a further cut of the same rank-ordered prefix -- w[0] is 1, so
+// "w[j] >= min_p" is transformers' MinPLogitsWarper relative to the most likely token, and the shorter of the two prefixes wins.
+__device__ __forceinline__ int topk_topp_pick(const SampleArgs& p, int row, const float* sval, float* w, int n, float min_p = 0.f) {
     const float invT = 1.f / p.temperature;
     const float mx = sval[0] * invT;
     float tot = 0.f;
@@ -174,7 +176,7 @@ __device__ __forceinline__ int topk_topp_pick(const SampleArgs& p, int row, cons
     float before = 0.f, kept = 0.f;
     int nk = 0;
     for (int j = 0; j < n; ++j) {
-        if (j > 0 && before >= p.top_p * tot) break;
+        if (j > 0 && (before >= p.top_p * tot || (min_p > 0.f && w[j] < min_p))) break;
         kept += w[j];
         before += w[j];
         ++nk;
@@ -274,6 +276,30 @@ struct LogpArgs {
 
 __device__ __forceinline__ bool whole_vocab(const SampleArgs& p) { return p.top_k <= 0 && p.temperature > 0.f; }
 
+// ---- iadr1_sample_ex: the same two kernels with a repetition penalty in front of the filter and a min_p cut behind it ----------------------------------
+// Both kernel bodies are templates on EX; iadr1_sample_logp launches the EX = false instantiations, in which none of the code below exists.  With EX the
+// filter sees x' (transformers' RepetitionPenaltyLogitsProcessor over the ids whose bit is set in `seen`), the log-prob keeps seeing the raw x.
+// Whole vocabulary with min_p > 0: whether a token is kept depends on the maximum of the WHOLE row, which stage 1 does not have, so stage 2 forms the
+// thresholded chunk masses itself (the block reads the row once more, chunk by chunk, with stage 1's thread -> id assignment and a tree no deeper than
+// stage 1's); stage 1 contributes the maxima and (m1, s1).
+struct ExArgs {
+    float min_p, pen;
+    unsigned* seen;     // [B, ld_seen] bitmap, bit id & 31 of word id >> 5
+    long long ld_seen;
+    int mark;
+};
+
+// one IEEE multiply or one IEEE divide; the empty asm keeps -ffp-contract from fusing the product into the subtraction that follows it
+__device__ __forceinline__ float penalised(float x, float pen) {
+    float r = x < 0.f ? x * pen : x / pen;
+    asm volatile("" : "+v"(r));
+    return r;
+}
+__device__ __forceinline__ bool seen_bit(const unsigned* srow, int g) { return (srow[g >> 5] >> (g & 31)) & 1u; }
+__device__ __forceinline__ void mark_pick(const ExArgs& e, int row, int pick) {     // one thread per row: a plain read-modify-write
+    if (e.mark) e.seen[(long long)row * e.ld_seen + (pick >> 5)] |= 1u << (pick & 31);
+}
+
 // inclusive scan over the lanes of a wave
 __device__ __forceinline__ float wave_incscan(float v) {
     const int lane = threadIdx.x & 63;
@@ -285,7 +311,8 @@ __device__ __forceinline__ float wave_incscan(float v) {
     return v;
 }
 
-__global__ __launch_bounds__(NT) void sample_logp_stage1(SampleArgs p, LogpArgs q) {
+template <bool EX>
+__device__ __forceinline__ void logp_stage1(const SampleArgs& p, const LogpArgs& q, const ExArgs& e) {
     __shared__ int hist[2048];
     __shared__ int sh_i[8];
     __shared__ float sh_f[16];
@@ -314,14 +341,26 @@ __global__ __launch_bounds__(NT) void sample_logp_stage1(SampleArgs p, LogpArgs 
 #pragma unroll
     for (int i = 0; i < ITEMS; ++i) mT = fmaxf(mT, val[i]);
     const float m1 = block_max<NT>(fmaxf(mT, xs), sh_f);
-    mT = block_max<NT>(mT, sh_f + 4);
-    const float invT = wv ? 1.f / p.temperature : 0.f;
     float s1 = 0.f, sT = 0.f;
     if (m1 > -INFINITY) {
 #pragma unroll
         for (int i = 0; i < ITEMS; ++i) s1 += expf(val[i] - m1);      // (padding and the suppressed slot hold -inf: they add 0)
         if (xs > -INFINITY) s1 += expf(xs - m1);
     }
+    if constexpr (EX) {
+        // (m1, s1) above are the raw row's; from here on val holds x' (-inf stays -inf: the suppressed slot and the padding need no test)
+        if (e.pen != 1.f) {
+            const unsigned* srow = e.seen + (long long)row * e.ld_seen;
+            mT = -INFINITY;
+#pragma unroll
+            for (int i = 0; i < ITEMS; ++i) {
+                if (idx[i] >= 0 && seen_bit(srow, idx[i])) val[i] = penalised(val[i], e.pen);
+                mT = fmaxf(mT, val[i]);
+            }
+        }
+    }
+    mT = block_max<NT>(mT, sh_f + 4);
+    const float invT = wv ? 1.f / p.temperature : 0.f;
     if (wv && mT > -INFINITY) {
 #pragma unroll
         for (int i = 0; i < ITEMS; ++i) sT += expf((val[i] - mT) * invT);
@@ -343,7 +382,8 @@ __global__ __launch_bounds__(NT) void sample_logp_stage1(SampleArgs p, LogpArgs 
     }
 }
 
-__global__ __launch_bounds__(NT) void sample_logp_stage2(SampleArgs p, LogpArgs q) {
+template <bool EX>
+__device__ __forceinline__ void logp_stage2(const SampleArgs& p, const LogpArgs& q, const ExArgs& e) {
     __shared__ int hist[2048];
     __shared__ int sh_i[8];
     __shared__ float sh_f[8];
@@ -367,7 +407,38 @@ __global__ __launch_bounds__(NT) void sample_logp_stage2(SampleArgs p, LogpArgs 
         const float invT = 1.f / p.temperature;
         const float mT = have ? pr[2] : -INFINITY, sT = have ? pr[3] : 0.f;
         const float MT = wave_max(mT);
-        const float mass = mT > -INFINITY ? sT * expf((mT - MT) * invT) : 0.f;
+        float mass = mT > -INFINITY ? sT * expf((mT - MT) * invT) : 0.f;
+        const int csize = (p.V + NCHUNK - 1) / NCHUNK;
+        const int per = (csize + NT - 1) / NT;
+        const unsigned* srow = nullptr;
+        float min_p = 0.f;
+        if constexpr (EX) {
+            if (e.pen != 1.f) srow = e.seen + (long long)row * e.ld_seen;
+            min_p = e.min_p;
+            if (min_p > 0.f) {
+                // the kept set hangs on MT: the chunk masses over the tokens with exp((x' - MT) / T) >= min_p, formed here.  Per chunk: <= ITEMS serial adds in
+                // the thread, 6 shuffle levels, 3 adds over the waves -- stage 1's depth; lane c of every wave ends up with chunk c's mass, the same bits in all four.
+                __shared__ float cm[NCHUNK][NT / WAVE];
+                for (int c = 0; c < NCHUNK; ++c) {
+                    const int c0 = c * csize, c1 = min(p.V, c0 + csize);
+                    float ts = 0.f;
+#pragma unroll
+                    for (int i = 0; i < ITEMS; ++i) {
+                        const int g = c0 + t * per + i;
+                        if (i < per && g < c1 && g != p.suppress) {
+                            float v = x[g];
+                            if (srow != nullptr && seen_bit(srow, g)) v = penalised(v, e.pen);
+                            const float w = expf((v - MT) * invT);
+                            ts += w >= min_p ? w : 0.f;
+                        }
+                    }
+                    ts = wave_sum(ts);
+                    if (lane == 0) cm[c][t >> 6] = ts;
+                }
+                __syncthreads();
+                mass = have ? ((cm[lane][0] + cm[lane][1]) + cm[lane][2]) + cm[lane][3] : 0.f;
+            }
+        }
         const float inc = wave_incscan(mass);
         const float total = __shfl(inc, NCHUNK - 1, WAVE);
         const unsigned long long sd = p.seed_ptr ? *p.seed_ptr : (((unsigned long long)p.seed_hi << 32) | p.seed_lo);
@@ -376,8 +447,6 @@ __global__ __launch_bounds__(NT) void sample_logp_stage2(SampleArgs p, LogpArgs 
         const unsigned long long hit = __ballot(have && inc > target), any = __ballot(have && mass > 0.f);
         const int chunk = hit ? (int)__builtin_ctzll(hit) : (any ? 63 - (int)__builtin_clzll(any) : 0);
         const float rest = target - (__shfl(inc, chunk, WAVE) - __shfl(mass, chunk, WAVE));     // what is left of the target inside the chunk
-        const int csize = (p.V + NCHUNK - 1) / NCHUNK;
-        const int per = (csize + NT - 1) / NT;
         const int c0 = chunk * csize, c1 = min(p.V, c0 + csize);
         float w[ITEMS];
         float ts = 0.f;
@@ -385,7 +454,17 @@ __global__ __launch_bounds__(NT) void sample_logp_stage2(SampleArgs p, LogpArgs 
         for (int i = 0; i < ITEMS; ++i) {
             const int g = c0 + t * per + i;
             const bool ok = i < per && g < c1 && g != p.suppress;      // (g < c1 <= V: the re-read stays inside the row)
-            w[i] = ok ? expf((x[g] - MT) * invT) : 0.f;
+            if constexpr (EX) {
+                w[i] = 0.f;
+                if (ok) {
+                    float v = x[g];
+                    if (srow != nullptr && seen_bit(srow, g)) v = penalised(v, e.pen);
+                    const float wi = expf((v - MT) * invT);
+                    w[i] = wi >= min_p ? wi : 0.f;
+                }
+            } else {
+                w[i] = ok ? expf((x[g] - MT) * invT) : 0.f;
+            }
             ts += w[i];
         }
         // exclusive block scan of the thread sums, in id order
@@ -412,6 +491,7 @@ __global__ __launch_bounds__(NT) void sample_logp_stage2(SampleArgs p, LogpArgs 
             const int pick = sh_i[0] != 0x7fffffff ? sh_i[0] : max(sh_i[1], 0);
             p.out[row] = pick;
             if (lp) *lp = x[pick] - lse;
+            if constexpr (EX) mark_pick(e, row, pick);
         }
         return;
     }
@@ -431,6 +511,7 @@ __global__ __launch_bounds__(NT) void sample_logp_stage2(SampleArgs p, LogpArgs 
             const int pick = n > 0 ? cidx[0] : 0;
             p.out[row] = pick;
             if (lp) *lp = x[pick] - lse;
+            if constexpr (EX) mark_pick(e, row, pick);
         }
         return;
     }
@@ -445,9 +526,30 @@ __global__ __launch_bounds__(NT) void sample_logp_stage2(SampleArgs p, LogpArgs 
     }
     __syncthreads();
     if (t == 0) {
-        const int pick = topk_topp_pick(p, row, sval, cval, n);
+        const int pick = topk_topp_pick(p, row, sval, cval, n, EX ? e.min_p : 0.f);
         p.out[row] = sidx[pick];
         if (lp) *lp = sraw[pick] - lse;
+        if constexpr (EX) mark_pick(e, row, sidx[pick]);
+    }
+}
+
+__global__ __launch_bounds__(NT) void sample_logp_stage1(SampleArgs p, LogpArgs q) { logp_stage1<false>(p, q, ExArgs{}); }
+__global__ __launch_bounds__(NT) void sample_logp_stage2(SampleArgs p, LogpArgs q) { logp_stage2<false>(p, q, ExArgs{}); }
+__global__ __launch_bounds__(NT) void sample_ex_stage1(SampleArgs p, LogpArgs q, ExArgs e) { logp_stage1<true>(p, q, e); }
+__global__ __launch_bounds__(NT) void sample_ex_stage2(SampleArgs p, LogpArgs q, ExArgs e) { logp_stage2<true>(p, q, e); }
+
+// iadr1_seen_init: one block per sequence zeroes its bitmap row, then ORs in the live tokens of its prompt (left-padded: columns [S - len, S)).
+__global__ __launch_bounds__(NT) void seen_init_kernel(const long long* ids, int S, const int* lengths, int G, int V, unsigned* seen, long long ld_seen) {
+    const int r = blockIdx.x, t = threadIdx.x;
+    unsigned* srow = seen + (long long)r * ld_seen;
+    for (long long i = t; i < ld_seen; i += NT) srow[i] = 0u;
+    __syncthreads();        // (the zeroes and the ORs below are this block's own: block-level ordering is enough)
+    const int b = r / G;
+    const int len = max(0, min(lengths[b], S));
+    const long long* prow = ids + (long long)b * S + (S - len);
+    for (int j = t; j < len; j += NT) {
+        const long long id = prow[j];
+        if (id >= 0 && id < V) atomicOr(&srow[id >> 5], 1u << (id & 31));
     }
 }
 
@@ -489,4 +591,40 @@ extern "C" int iadr1_sample_logp(const float* logits, long long ld, long long* o
     hipLaunchKernelGGL(sample_logp_stage1, dim3(NCHUNK, B), dim3(NT), 0, stream, p, q);
     hipLaunchKernelGGL(sample_logp_stage2, dim3(B), dim3(NT), 0, stream, p, q);
     return iadr1_check_launch("sample_logp");
+}
+
+extern "C" long long iadr1_sample_ex_workspace_bytes(int B) { return iadr1_sample_logp_workspace_bytes(B); }
+
+extern "C" int iadr1_sample_ex(const float* logits, long long ld, long long* out, float* logp_out, long long ld_logp, int logp_cols, void* workspace, int B,
+                               int V, float temperature, int top_k, float top_p, float min_p, float repetition_penalty, unsigned* seen, long long ld_seen,
+                               int mark_seen, int suppress_token, unsigned long long seed, unsigned step, const unsigned* step_ptr,
+                               const unsigned long long* seed_ptr, hipStream_t stream) {
+    IADR1_REQUIRE(min_p >= 0.f && min_p < 1.f, "sample_ex: min_p must be in [0,1) (got %g)", (double)min_p);
+    IADR1_REQUIRE(repetition_penalty > 0.f && repetition_penalty <= 3.402823466e38f, "sample_ex: repetition_penalty must be finite and > 0 (got %g)", (double)repetition_penalty);
+    IADR1_REQUIRE((repetition_penalty == 1.f && !mark_seen) || (seen != nullptr && ld_seen >= ((long long)V + 31) / 32),
+                  "sample_ex: repetition_penalty != 1 and mark_seen need a seen bitmap [B, ld_seen] with ld_seen >= ceil(V / 32) (got %s, ld_seen %lld, V %d)",
+                  seen ? "a buffer" : "NULL", ld_seen, V);
+    IADR1_REQUIRE(top_p > 0.f && top_p <= 1.f, "sample_ex: top_p must be in (0,1]");
+    IADR1_REQUIRE(top_k > 0 || top_p == 1.f, "sample_ex: top_k <= 0 samples the whole vocabulary and takes top_p = 1 only (got %g): a nucleus over all V tokens is not built", (double)top_p);
+    IADR1_REQUIRE(B > 0 && V > 0 && workspace != nullptr, "sample_ex: empty problem or missing workspace (iadr1_sample_ex_workspace_bytes)");
+    IADR1_REQUIRE(V <= NCHUNK * NT * ITEMS, "sample_ex: V=%d exceeds the built maximum %d", V, NCHUNK * NT * ITEMS);
+    IADR1_REQUIRE(top_k <= MAXK, "sample_ex: top_k=%d exceeds the built maximum %d", top_k, MAXK);
+    IADR1_REQUIRE(logp_out == nullptr || (logp_cols > 0 && ld_logp >= logp_cols), "sample_ex: logp_out needs logp_cols > 0 and ld_logp >= logp_cols");
+    float* cv = (float*)workspace;
+    int* ci = (int*)(cv + (long long)B * NCHUNK * MAXK);
+    float* part = (float*)(ci + (long long)B * NCHUNK * MAXK);
+    SampleArgs p{logits, ld, out, cv, ci, B, V, temperature, top_p, top_k, suppress_token, (uint32_t)seed, (uint32_t)(seed >> 32), step, step_ptr, seed_ptr};
+    LogpArgs q{part, logp_out, ld_logp, logp_cols};
+    ExArgs e{min_p, repetition_penalty, seen, ld_seen, mark_seen != 0};
+    hipLaunchKernelGGL(sample_ex_stage1, dim3(NCHUNK, B), dim3(NT), 0, stream, p, q, e);
+    hipLaunchKernelGGL(sample_ex_stage2, dim3(B), dim3(NT), 0, stream, p, q, e);
+    return iadr1_check_launch("sample_ex");
+}
+
+extern "C" int iadr1_seen_init(const long long* ids, int S, const int* lengths, int Bp, int G, int V, unsigned* seen, long long ld_seen, hipStream_t stream) {
+    IADR1_REQUIRE(ids != nullptr && lengths != nullptr && seen != nullptr, "seen_init: ids, lengths and seen are required");
+    IADR1_REQUIRE(S > 0 && Bp > 0 && G > 0 && V > 0, "seen_init: empty problem (S=%d, Bp=%d, G=%d, V=%d)", S, Bp, G, V);
+    IADR1_REQUIRE(ld_seen >= ((long long)V + 31) / 32, "seen_init: ld_seen=%lld is less than ceil(V / 32) = %lld", ld_seen, ((long long)V + 31) / 32);
+    hipLaunchKernelGGL(seen_init_kernel, dim3(Bp * G), dim3(NT), 0, stream, ids, S, lengths, G, V, seen, ld_seen);
+    return iadr1_check_launch("seen_init");
 }

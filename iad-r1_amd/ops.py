@@ -698,6 +698,42 @@ def sample_logp(logits32, temperature, top_k, top_p, seed, step, suppress_token=
     return o, logp_out
 
 
+_sample_ex_ws = {}
+
+
+def sample_ex(logits32, temperature, top_k, top_p, seed, step, min_p=0.0, repetition_penalty=1.0, seen=None, mark_seen=False, suppress_token=-1, step_ptr=None, out=None,
+              seed_ptr=None, logp_out=None, want_logp=True):
+    """iadr1_sample_ex: `sample_logp` with a repetition penalty over the per-sequence bitmap `seen` ([B, >= ceil(V / 32)] 32-bit words: int32 or uint32) in front
+    of the filter and a min_p cut behind it; mark_seen: the pick's bit is set in seen[row] inside the call.  logp_out keeps sample_logp's meaning (raw logits,
+    temperature 1, no penalty, no filter).  With min_p 0, repetition_penalty 1 and mark_seen False the result is bit-equal to sample_logp's.  Returns (ids, logp_out or None)."""
+    B, V = logits32.shape
+    o = out if out is not None else torch.empty(B, dtype=torch.int64, device=logits32.device)
+    if logp_out is None and want_logp:
+        assert step_ptr is None and int(step) == 0, "sample_ex: give logp_out [B, cols] when the step (the column) is not 0"
+        logp_out = torch.zeros(B, 1, dtype=F32, device=logits32.device)
+    if seen is not None:
+        assert seen.dim() == 2 and seen.shape[0] == B and seen.element_size() == 4 and seen.stride(1) == 1, "sample_ex: seen is [B, words] of 32-bit words"
+    key = (B, logits32.device)
+    ws = _sample_ex_ws.get(key)
+    if ws is None:
+        ws = torch.empty(hip.lib().iadr1_sample_ex_workspace_bytes(B), dtype=torch.uint8, device=logits32.device)
+        _sample_ex_ws[key] = ws
+    hip.call("sample_ex", logits32, _ld(logits32), o, logp_out, _ld(logp_out) if logp_out is not None else 0, logp_out.shape[1] if logp_out is not None else 0, ws, B, V,
+             float(temperature), int(top_k), float(top_p), float(min_p), float(repetition_penalty), seen, seen.stride(0) if seen is not None else 0, int(bool(mark_seen)),
+             int(suppress_token), int(seed), int(step), step_ptr, seed_ptr)
+    return o, logp_out
+
+
+def seen_init(ids, lengths, G, V, seen):
+    """iadr1_seen_init: seen [Bp * G, >= ceil(V / 32)] 32-bit words <- the live tokens of the left-padded prompts ids [Bp, S] int64 (lengths [Bp] int32, on the
+    device), every prompt's row repeated for its G sequences; ids outside [0, V) are ignored."""
+    Bp, S = ids.shape
+    assert ids.dtype == torch.int64 and ids.stride(1) == 1 and ids.stride(0) == S and lengths.dtype == torch.int32 and lengths.numel() == Bp
+    assert seen.dim() == 2 and seen.shape[0] >= Bp * G and seen.element_size() == 4 and seen.stride(1) == 1
+    hip.call("seen_init", ids, S, lengths, Bp, int(G), int(V), seen, seen.stride(0))
+    return seen
+
+
 def rope_kv_store(qkv, cos, sin, slot, kcache, vcache, Hq, Hkv, D):
     hip.call("rope_kv_store", qkv, _ld(qkv), cos, sin, slot, kcache, vcache, qkv.shape[0], Hq, Hkv, D)
 

@@ -102,8 +102,9 @@ class Rollout:
         self.trace = None           # training arena filled by the decode steps (generate(train_trace=...)); part of the captured graph
         self.decode_events = None   # bench.py sets a list: (start event, end event, decode steps, sum of prompt lengths over sequences) per call
         self.seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.sampling = dict(temperature=0.9, top_k=50, top_p=0.9, suppress=-1, eos=c.eos_token_id, pad=c.pad_token_id, logps=False)
+        self.sampling = dict(temperature=0.9, top_k=50, top_p=0.9, suppress=-1, eos=c.eos_token_id, pad=c.pad_token_id, logps=False, min_p=0.0, repetition_penalty=1.0)
         self.logps = None           # [N, max_new] fp32 log-probs of the sampled tokens (generate(return_logps=True)): column = the step counter, like out_tokens
+        self.seen = None            # [N, ceil(V / 32)] 32-bit words (generate(repetition_penalty != 1)): bit id & 31 of word id >> 5 = the sequence has seen token id
 
     # ---- one decode step (graph body) -------------------------------------------------------------------------
     def _decode_step(self):
@@ -172,7 +173,13 @@ class Rollout:
 
     def _sample_and_advance(self):
         s = self.sampling
-        if s["logps"] or (s["top_k"] <= 0 and s["temperature"] > 0):
+        if s["min_p"] != 0.0 or s["repetition_penalty"] != 1.0:
+            # iadr1_sample_ex: the penalty reads self.seen and the pick's bit is set inside the sampler's second launch, on this stream, part of the graph
+            pen = s["repetition_penalty"] != 1.0
+            ops.sample_ex(self.logits, s["temperature"], s["top_k"], s["top_p"], 0, 0, min_p=s["min_p"], repetition_penalty=s["repetition_penalty"], seen=self.seen if pen else None,
+                          mark_seen=pen, suppress_token=s["suppress"], step_ptr=self.step, out=self.sampled, seed_ptr=self.seed_dev, logp_out=self.logps if s["logps"] else None,
+                          want_logp=False)
+        elif s["logps"] or (s["top_k"] <= 0 and s["temperature"] > 0):
             # iadr1_sample_logp: the whole-vocabulary draw and / or the log-prob of the pick; the default path below is the launch pair it has always been
             ops.sample_logp(self.logits, s["temperature"], s["top_k"], s["top_p"], 0, 0, suppress_token=s["suppress"], step_ptr=self.step, out=self.sampled, seed_ptr=self.seed_dev,
                             logp_out=self.logps if s["logps"] else None, want_logp=False)
@@ -206,11 +213,14 @@ class Rollout:
                 ops.hip.set_decode_cus(0)
 
     def _generate(self, plan: TextPlan, img_embeds, G: int, max_new: int, temperature=0.9, top_k=50, top_p=0.9, seed=0, suppress_eos=False,
-                  stop_at_eos=True, train_carry=None, train_trace=False, shadow=None, return_logps=False):
+                  stop_at_eos=True, train_carry=None, train_trace=False, shadow=None, return_logps=False, min_p=0.0, repetition_penalty=1.0):
         """plan: the Bp left-padded prompts.  Returns completion ids [Bp*G, max_new] (prompt-major order: p0 x G,
         p1 x G, ...), pad after the first EOS.
         top_k <= 0: the whole vocabulary (top_p must then be 1.0).  return_logps: returns (ids, logps) -- logps [Bp*G, max_new] fp32 on the device, the
         temperature-1 unfiltered log-prob of every sampled token under the logits it was sampled from (iadr1_sample_logp), 0 after a sequence's first EOS.
+        min_p, repetition_penalty: trl's GRPOConfig options (iadr1_sample_ex; transformers' order: penalty, temperature, top-k, top-p, min_p).  The penalty is over
+        the live prompt tokens (image placeholders included) and the tokens sampled so far, kept as a bitmap on the device (self.seen) that the sampler updates
+        inside the captured step.  Greedy decoding honours the penalty and ignores min_p.  The log-probs of return_logps stay unpenalised and unfiltered.
         shadow: an overlap.ChunkedRefPass -- the frozen reference's teacher-forced pass over the tokens produced so far is enqueued on ITS stream every
         `shadow.steps` decode steps, behind one event per chunk (the caller reads shadow.logp after shadow.join())."""
         e, c = self.e, self.e.cfg
@@ -224,9 +234,17 @@ class Rollout:
         self.seed_dev.fill_(int(seed) & 0x7FFFFFFFFFFFFFFF)   # device-resident: a new seed per rollout does not invalidate the captured graph
         if int(top_k) <= 0 and float(temperature) > 0 and float(top_p) != 1.0:
             raise ValueError(f"top_k <= 0 samples the whole vocabulary and needs top_p == 1.0 (got {top_p}): a nucleus over all tokens is not built")
+        min_p, repetition_penalty = float(min_p or 0.0), float(repetition_penalty)
+        if not (0.0 <= min_p < 1.0):
+            raise ValueError(f"min_p must be in [0, 1), got {min_p}")
+        if not (np.isfinite(repetition_penalty) and repetition_penalty > 0.0):
+            raise ValueError(f"repetition_penalty must be finite and > 0, got {repetition_penalty}")
         sampling = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p),
                         suppress=c.eos_token_id if suppress_eos else -1, eos=c.eos_token_id if stop_at_eos and not suppress_eos else -1, pad=c.pad_token_id,
-                        logps=bool(return_logps))
+                        logps=bool(return_logps), min_p=min_p, repetition_penalty=repetition_penalty)
+        if repetition_penalty != 1.0 and self.seen is None:
+            self.seen = torch.zeros(self.N, (c.vocab_size + 31) // 32, dtype=torch.int32, device=dev)
+            self.graph = None          # (the buffer is a kernel argument of the captured sampler)
         if return_logps:
             if self.logps is None:
                 self.logps = torch.zeros(self.N, self.max_new, dtype=F32, device=dev)
@@ -342,12 +360,16 @@ class Rollout:
         self.finished.zero_()
         self.step.zero_()
         self.out_tokens.fill_(c.pad_token_id)
+        if repetition_penalty != 1.0:   # every rollout starts from its prompts' tokens: what the previous one sampled (and a capture's two extra steps) is gone
+            ops.seen_init(plan.ids.view(Bp, S), torch.from_numpy(np.asarray(lengths).astype(np.int32)).pin_memory().to(dev, non_blocking=True), G, c.vocab_size, self.seen)
         self._sample_and_advance()                                           # token 0 from the prefill logits
         # ---- decode ----------------------------------------------------------------------------------------------
         if self.use_graph and self.graph is None:
             state = (self.pos, self.ctx_len, self.slot, self.finished, self.step, self.cur_tok, self.out_tokens, self.cos, self.sin, self.all_done)
             if return_logps:
                 state = state + (self.logps,)
+            if repetition_penalty != 1.0:
+                state = state + (self.seen,)     # (the warm-up and the capture mark two tokens nobody sampled)
             saved = [t.clone() for t in state]
             import time as _time
             torch.cuda.synchronize()

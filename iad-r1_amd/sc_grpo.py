@@ -44,6 +44,14 @@ class GRPOArgs:
     temperature: float = 0.9
     top_k: int = 50            # hard-coded in the reference (REF:353-358); <= 0: the whole vocabulary (needs top_p == 1.0, checked when the engine is built)
     top_p: float = 0.9
+    # trl.GRPOConfig's names (REF trl/trl/trainer/grpo_config.py).  Both are filters of the rollout's sampler (iadr1_sample_ex), applied in transformers' order --
+    # repetition penalty, temperature, top-k, top-p, min_p -- and both are off by default: the rollout then issues the launches it always has.  The loss does not
+    # change; the rollout's log-probs (rollout_logps, rollout_is_cap) stay temperature-1, unpenalised and unfiltered.
+    # min_p in [0, 1) (None: 0): a token stays iff its probability is >= min_p x the most likely token's; the one truncation top_k <= 0 can be combined with.
+    # repetition_penalty (finite, > 0; 1 = off): logits of the tokens a sequence has already seen (prompt, image placeholders included, and its completion so
+    # far) are divided by it when positive and multiplied when negative (transformers' RepetitionPenaltyLogitsProcessor).  Greedy rollouts keep it and drop min_p.
+    min_p: float | None = 0.0
+    repetition_penalty: float = 1.0
     # the rollout also returns the log-prob of every token it sampled (temperature 1, unfiltered: the quantity the loss scores); the step's metrics gain
     # rollout/logp_abs_diff_mean, rollout/logp_abs_diff_max and rollout/kl against the policy log-probs of the loss.  Nothing in the loss or the gradients changes.
     rollout_logps: bool = False
@@ -110,6 +118,17 @@ def check_reuse_args(who: str, num_iterations, epsilon, epsilon_high):
         raise ValueError(f"{who}.epsilon must be finite and in [0, 1) (got {epsilon}): the lower clip bound 1 - epsilon of a probability ratio must stay positive")
     if epsilon_high is not None and not (math.isfinite(epsilon_high) and epsilon_high >= 0.0):
         raise ValueError(f"{who}.epsilon_high must be None (= epsilon) or finite and >= 0 (got {epsilon_high})")
+
+
+def check_sampler_args(who: str, min_p, repetition_penalty):
+    """min_p / repetition_penalty of GRPOArgs and GRPOConfig (`who` names the class in the message): the ranges iadr1_sample_ex accepts.  Returns min_p with
+    trl's None read as 0."""
+    mp = 0.0 if min_p is None else float(min_p)
+    if not (0.0 <= mp < 1.0):       # (a NaN fails both compares)
+        raise ValueError(f"{who}.min_p must be in [0, 1) or None (got {min_p}): it is a fraction of the most likely token's probability, and 1 would keep that token only")
+    if not (math.isfinite(repetition_penalty) and repetition_penalty > 0.0):
+        raise ValueError(f"{who}.repetition_penalty must be finite and > 0 (got {repetition_penalty}); 1 switches it off")
+    return mp
 
 
 LOSS_TYPES = ("grpo", "bnpo", "dr_grpo")
@@ -398,6 +417,7 @@ class SCGRPOEngine:
         if args.rollout_is_cap > 0 and cfg.is_llava and args.llava_rotate_right_padded_rows:
             raise ValueError("GRPOArgs.rollout_is_cap with llava_rotate_right_padded_rows: that path scores a rotated window, whose columns do not line up with the "
                              "rollout's log-probs; set llava_rotate_right_padded_rows=False to weight the completion tokens themselves")
+        check_sampler_args("GRPOArgs", args.min_p, args.repetition_penalty)
         check_reuse_args("GRPOArgs", args.num_iterations, args.epsilon, args.epsilon_high)
         check_objective_args("GRPOArgs", args.loss_type, args.mask_truncated_completions, args.suppress_eos)
         if ref is None and args.beta != 0:
@@ -483,7 +503,8 @@ class SCGRPOEngine:
                 print("[iadr1] sequential step: the frozen reference's pass runs after the rollout, on the whole device", file=sys.stderr, flush=True)
         toks = self._rollout.generate(plan, img_pol, a.num_generations, a.max_completion_length, temperature=0.0 if greedy else a.temperature,
                                       top_k=a.top_k, top_p=a.top_p, seed=a.seed + 1000003 * self.opt_step + 7919 * self.accum, suppress_eos=a.suppress_eos,
-                                      train_carry=train_carry, train_trace=trace, shadow=shadow, return_logps=a.wants_rollout_logps)
+                                      train_carry=train_carry, train_trace=trace, shadow=shadow, return_logps=a.wants_rollout_logps,
+                                      min_p=0.0 if greedy else (a.min_p or 0.0), repetition_penalty=a.repetition_penalty)
         self.last_rollout_logps = None
         if a.wants_rollout_logps:
             toks, self.last_rollout_logps = toks

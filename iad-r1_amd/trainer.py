@@ -25,7 +25,7 @@ import torch
 
 from . import schedule
 from .params import ParamStore, VLMConfig
-from .sc_grpo import GRPOArgs, SCGRPOEngine, check_objective_args, check_reuse_args
+from .sc_grpo import GRPOArgs, SCGRPOEngine, check_objective_args, check_reuse_args, check_sampler_args
 
 
 @dataclass
@@ -43,6 +43,8 @@ class GRPOConfig:
     temperature: float = 0.9
     top_k: int = 50                 # (vLLM SamplingParams of REF sc_grpo_trainer.py:353-358: top_k 50, top_p 0.9); <= 0: the whole vocabulary, needs top_p 1.0
     top_p: float = 0.9
+    min_p: Optional[float] = 0.0    # trl.GRPOConfig's name: keep the tokens with probability >= min_p x the most likely one's; in [0, 1), None = 0 = off (GRPOArgs.min_p)
+    repetition_penalty: float = 1.0     # trl.GRPOConfig's name: transformers' repetition penalty over prompt + completion so far; finite, > 0, 1 = off (GRPOArgs.repetition_penalty)
     rollout_logps: bool = False     # log rollout/logp_abs_diff_mean|max and rollout/kl: sampled vs scored log-probs of the rollout's tokens (GRPOArgs.rollout_logps)
     rollout_is_cap: float = 0.0     # > 0 (then >= 1): weight every per-token loss term by min(exp(scored - sampled log-prob), cap); 0 = off (GRPOArgs.rollout_is_cap)
     rollout_is_level: str = "token"     # "token" | "sequence" (one weight per row, from the row's mean log-ratio)
@@ -342,6 +344,7 @@ class SCGRPOTrainer:
             args = GRPOConfig(output_dir=f"{os.path.basename(name.rstrip('/'))}-GRPO")
         self.args = args
         check_reuse_args("GRPOConfig", args.num_iterations, args.epsilon, args.epsilon_high)
+        check_sampler_args("GRPOConfig", args.min_p, args.repetition_penalty)
         check_objective_args("GRPOConfig", args.loss_type)
         if args.save_steps and args.save_steps % args.num_iterations != 0:
             raise ValueError(f"GRPOConfig.save_steps ({args.save_steps}) must be a multiple of num_iterations ({args.num_iterations}): a checkpoint holds no cached "
@@ -408,7 +411,7 @@ class SCGRPOTrainer:
             group = dist.group.WORLD
         self.engine = SCGRPOEngine(self.cfg, self.policy, self.ref, GRPOArgs(
             num_generations=args.num_generations, max_prompt_length=args.max_prompt_length, max_completion_length=args.max_completion_length,
-            beta=args.beta, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, rollout_logps=args.rollout_logps, rollout_is_cap=args.rollout_is_cap, rollout_is_level=args.rollout_is_level,
+            beta=args.beta, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, min_p=args.min_p, repetition_penalty=args.repetition_penalty, rollout_logps=args.rollout_logps, rollout_is_cap=args.rollout_is_cap, rollout_is_level=args.rollout_is_level,
             num_iterations=args.num_iterations, epsilon=args.epsilon, epsilon_high=args.epsilon_high, loss_type=args.loss_type, scale_rewards=args.scale_rewards,
             mask_truncated_completions=args.mask_truncated_completions, learning_rate=args.learning_rate, weight_decay=args.weight_decay,
             adam_beta1=args.adam_beta1, adam_beta2=args.adam_beta2, adam_epsilon=args.adam_epsilon, max_grad_norm=args.max_grad_norm,

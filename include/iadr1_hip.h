@@ -361,6 +361,33 @@ long long iadr1_sample_logp_workspace_bytes(int B);
 int iadr1_sample_logp(const float* logits, long long ld, long long* out, float* logp_out, long long ld_logp, int logp_cols, void* workspace, int B,
                       int V, float temperature, int top_k, float top_p, int suppress_token, unsigned long long seed, unsigned step,
                       const unsigned* step_ptr, const unsigned long long* seed_ptr, iadr1_stream_t stream);
+/* iadr1_sample_ex: iadr1_sample_logp with trl's GRPOConfig(repetition_penalty, min_p) in the filter.  Order as in transformers' processors and warpers:
+ * repetition penalty -> temperature -> top-k -> top-p -> min_p.
+ *   seen: [B, ld_seen] 32-bit words, ld_seen >= ceil(V / 32); bit (id & 31) of word (id >> 5) of row b set = sequence b has seen token id (prompt or completion).
+ *   repetition_penalty (finite, > 0; 1 = off): RepetitionPenaltyLogitsProcessor -- for a seen id  x' = x < 0 ? x * pen : x / pen, one IEEE fp32 multiply or
+ *     divide (no reciprocal); unseen ids keep x; -inf stays -inf; suppress_token is forced to -inf AFTER the penalty.  Everything the filter reads is x': the
+ *     top-k candidates, the whole-vocabulary weights, the greedy argmax (temperature <= 0 honours the penalty and ignores min_p).
+ *   min_p in [0, 1) (0 = off): MinPLogitsWarper -- with w_i = exp((x'_i - max x') / T), a token is kept iff w_i >= min_p.  top_k in 1..64: a further cut of the
+ *     rank-ordered candidates behind the top-p cut (both are prefixes, the shorter wins, rank 0 always stays).  top_k <= 0 (top_p must be 1): dropped tokens
+ *     have weight 0 in the inverse CDF in id order over the kept ones; this is the truncation the whole-vocabulary path has (min_p needs no sort).
+ *   logp_out: UNCHANGED in meaning -- the temperature-1 log-softmax of the RAW logits at the pick (no penalty, no filter, no suppression), what
+ *     iadr1_logprob_rows scores; an importance weight against it (iadr1_grpo_loss_is) keeps correcting the engine mismatch only, not the penalty or min_p.
+ *   mark_seen != 0: after the pick, one thread per row sets the pick's bit in seen[row] (inside stage 2, on the sampler's stream, graph-capturable).  Rows the
+ *     caller regards as finished are marked with whatever was drawn for them: harmless, their draws are discarded.
+ *   min_p == 0, repetition_penalty == 1, mark_seen == 0: ids and logp_out are bit-equal to iadr1_sample_logp (the same device code), seen is not touched and
+ *     may be NULL.  Refused on the host, before any launch, one message each: min_p outside [0, 1); repetition_penalty not finite or <= 0;
+ *     repetition_penalty != 1 or mark_seen without seen or with ld_seen < ceil(V / 32); and everything iadr1_sample_logp refuses.
+ *   Same Philox stream (seed; row, step), step_ptr / seed_ptr, two launches; workspace: iadr1_sample_ex_workspace_bytes(B).  No allocation, no host sync, no
+ *     float atomics: legal under hipGraph capture. */
+long long iadr1_sample_ex_workspace_bytes(int B);
+int iadr1_sample_ex(const float* logits, long long ld, long long* out, float* logp_out, long long ld_logp, int logp_cols, void* workspace, int B,
+                    int V, float temperature, int top_k, float top_p, float min_p, float repetition_penalty, unsigned* seen, long long ld_seen,
+                    int mark_seen, int suppress_token, unsigned long long seed, unsigned step, const unsigned* step_ptr,
+                    const unsigned long long* seed_ptr, iadr1_stream_t stream);
+/* iadr1_seen_init: the seen bitmap of a rollout's Bp * G sequences from its Bp left-padded prompts ids [Bp, S]: zeroes rows [0, Bp * G) (ld_seen words each) and,
+ * for sequence r, sets the bits of the lengths[r / G] live tokens of prompt row r / G (columns [S - len, S): image placeholder ids included, left padding
+ * not).  Ids outside [0, V) are ignored, never written.  One launch; integer atomic OR on global memory. */
+int iadr1_seen_init(const long long* ids, int S, const int* lengths, int Bp, int G, int V, unsigned* seen, long long ld_seen, iadr1_stream_t stream);
 
 /* ---- device-resident rollout bookkeeping (one decode step = a fixed, graph-replayable launch sequence) ------
  * rope_table: cos/sin [B, half] for the current text positions (TF:1165-1176: pos = kv_len + rope_delta).

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Measurements around iadr1_sample_logp (profiles/EXPERIMENTS.md "Whole-vocabulary sampling and rollout log-probs"):
   sampler   the two sampler launches on the decode shape (64 x 151936 fp32, rotating buffers), HIP events, us per call: the old entry point, the new one with
-            top-k 50 + log-probs, and the whole vocabulary (top_k = 0) + log-probs
+            top-k 50 + log-probs, and the whole vocabulary (top_k = 0) + log-probs; then iadr1_sample_ex on the same inputs, neutral and with penalty / min_p
   decode    ms per decode step of the 3B rollout (8 prompts x G = 8, HIP events around the graph replays) with return_logps off / on / top_k = 0
   metrics   rollout/logp_abs_diff_mean|max and rollout/kl of one SC-GRPO step at 3B shapes (8 x 8 x 256 tokens), for the decode weights given by --decode_weights
 Usage: python tools/rollout_logps_probe.py sampler | decode [--layers N] | metrics [--layers N] [--decode_weights fp8]"""
@@ -51,6 +51,14 @@ if a.what == "sampler":
         new = timed(lambda i: ops.sample_logp(lg[i % 6], 0.9, 50, 0.9, 1234, i % 256, out=out, logp_out=lp))
         wv = timed(lambda i: ops.sample_logp(lg[i % 6], 0.9, 0, 1.0, 1234, i % 256, out=out, logp_out=lp))
         print(f"sampler, us per call (stage 1 + stage 2): sample_topk_topp {old:.1f} | sample_logp top-k 50 + logp {new:.1f} | sample_logp whole vocabulary + logp {wv:.1f}", flush=True)
+        # iadr1_sample_ex on the same inputs (profiles/EXPERIMENTS.md "min_p and repetition_penalty"): a bitmap of 700 seen ids per row, marked further by every call
+        if rep == 0:
+            seen = torch.zeros(64, (151936 + 31) // 32, dtype=torch.int32, device=dev)
+            pr = torch.randint(0, 151936, (64, 700), device=dev)
+            seen.view(-1).scatter_(0, (torch.arange(64, device=dev)[:, None] * seen.shape[1] + (pr >> 5)).view(-1), torch.ones(64 * 700, dtype=torch.int32, device=dev))
+        ex = lambda k, p, mp, pen: timed(lambda i: ops.sample_ex(lg[i % 6], 0.9, k, p, 1234, i % 256, min_p=mp, repetition_penalty=pen, seen=seen, mark_seen=pen != 1.0, out=out, logp_out=lp))
+        print(f"sample_ex, us per call: neutral top-k 50 {ex(50, 0.9, 0.0, 1.0):.1f} | top-k 50 + penalty 1.3 + min_p 0.05 {ex(50, 0.9, 0.05, 1.3):.1f} | whole vocabulary: neutral {ex(0, 1.0, 0.0, 1.0):.1f}, "
+              f"penalty 1.3 {ex(0, 1.0, 0.0, 1.3):.1f}, min_p 0.05 {ex(0, 1.0, 0.05, 1.0):.1f}, penalty 1.3 + min_p 0.05 {ex(0, 1.0, 0.05, 1.3):.1f}", flush=True)
     sys.exit(0)
 
 import bench  # noqa: E402

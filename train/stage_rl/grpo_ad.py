@@ -81,6 +81,11 @@ def build_parser():
     p.add_argument("--temperature", type=float, default=0.9)
     p.add_argument("--top_k", type=int, default=50, help="rollout sampler (the reference hard-codes 50); <= 0: the whole vocabulary, needs --top_p 1.0")
     p.add_argument("--top_p", type=float, default=0.9)
+    p.add_argument("--min_p", type=float, default=0.0,
+                   help="rollout sampler: keep the tokens whose probability is >= min_p x the most likely token's (after temperature, top-k and top-p); in [0, 1), 0 = off. "
+                        "The truncation that goes with --top_k 0")
+    p.add_argument("--repetition_penalty", type=float, default=1.0,
+                   help="rollout sampler: transformers' repetition penalty over the prompt and the completion so far (> 1 discourages repeats); finite and > 0, 1 = off")
     p.add_argument("--rollout_logps", nargs="?", default=False, const=True, type=lambda v: str(v).lower() in ("1", "true", "yes"),
                    help="log rollout/logp_abs_diff_mean|max and rollout/kl: the sampler's log-probs of the tokens it drew against the loss's policy log-probs")
     p.add_argument("--rollout_is_cap", type=float, default=0.0,

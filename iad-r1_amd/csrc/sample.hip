@@ -300,6 +300,24 @@ __device__ __forceinline__ void mark_pick(const ExArgs& e, int row, int pick) { 
     if (e.mark) e.seen[(long long)row * e.ld_seen + (pick >> 5)] |= 1u << (pick & 31);
 }
 
+// ---- iadr1_sample_guided: the same two kernels with a per-row automaton in front of everything the filter does --------------------------------------------------
+// One more template flag, GD; the four kernels above launch the GD = false instantiations, in which none of the code below exists.  Row b is in state[b]; the
+// filter sees -inf wherever bit id of allow[state[b]] is clear (before the penalty: -inf stays -inf through it and through the temperature), the log-prob keeps
+// seeing the raw x.  The state is read once, at entry, into a register in both stages; stage 2's thread 0 moves it along trans after the pick.
+struct GuideArgs {
+    int* state;             // [B], 0 <= state[b] < S
+    const unsigned* allow;  // [S, ld_allow] bitmap, bit id & 31 of word id >> 5 (the layout of `seen`)
+    const short* trans;     // [S, ld_trans]: the state behind (s, id), -1 where id is not allowed
+    long long ld_allow, ld_trans;
+    int S;
+};
+// (the clamp costs two instructions and keeps the allow row inside its table whatever the caller left in state[])
+__device__ __forceinline__ int guide_state(const GuideArgs& g, int row) { return min(max(g.state[row], 0), g.S - 1); }
+__device__ __forceinline__ void guide_advance(const GuideArgs& g, int row, int st, int pick) {    // one thread per row: a plain load and a plain store
+    const int n = pick >= 0 ? (int)g.trans[(long long)st * g.ld_trans + pick] : -1;
+    g.state[row] = (n >= 0 && n < g.S) ? n : st;   // a fallback pick (every allowed logit -inf) may be a disallowed id: the state then stays where it is, in range
+}
+
 // inclusive scan over the lanes of a wave
 __device__ __forceinline__ float wave_incscan(float v) {
     const int lane = threadIdx.x & 63;
@@ -311,8 +329,8 @@ __device__ __forceinline__ float wave_incscan(float v) {
     return v;
 }
 
-template <bool EX>
-__device__ __forceinline__ void logp_stage1(const SampleArgs& p, const LogpArgs& q, const ExArgs& e) {
+template <bool EX, bool GD = false>
+__device__ __forceinline__ void logp_stage1(const SampleArgs& p, const LogpArgs& q, const ExArgs& e, const GuideArgs& gd = GuideArgs{}) {
     __shared__ int hist[2048];
     __shared__ int sh_i[8];
     __shared__ float sh_f[16];
@@ -346,6 +364,16 @@ __device__ __forceinline__ void logp_stage1(const SampleArgs& p, const LogpArgs&
 #pragma unroll
         for (int i = 0; i < ITEMS; ++i) s1 += expf(val[i] - m1);      // (padding and the suppressed slot hold -inf: they add 0)
         if (xs > -INFINITY) s1 += expf(xs - m1);
+    }
+    if constexpr (GD) {
+        // (m1, s1) above are the raw row's; the automaton's mask comes first of all the filter does
+        const unsigned* arow = gd.allow + (long long)guide_state(gd, row) * gd.ld_allow;
+        mT = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < ITEMS; ++i) {
+            if (idx[i] >= 0 && !seen_bit(arow, idx[i])) val[i] = -INFINITY;
+            mT = fmaxf(mT, val[i]);
+        }
     }
     if constexpr (EX) {
         // (m1, s1) above are the raw row's; from here on val holds x' (-inf stays -inf: the suppressed slot and the padding need no test)
@@ -382,8 +410,8 @@ __device__ __forceinline__ void logp_stage1(const SampleArgs& p, const LogpArgs&
     }
 }
 
-template <bool EX>
-__device__ __forceinline__ void logp_stage2(const SampleArgs& p, const LogpArgs& q, const ExArgs& e) {
+template <bool EX, bool GD = false>
+__device__ __forceinline__ void logp_stage2(const SampleArgs& p, const LogpArgs& q, const ExArgs& e, const GuideArgs& gd = GuideArgs{}) {
     __shared__ int hist[2048];
     __shared__ int sh_i[8];
     __shared__ float sh_f[8];
@@ -397,6 +425,12 @@ __device__ __forceinline__ void logp_stage2(const SampleArgs& p, const LogpArgs&
     const float* x = p.logits + (long long)row * p.ld;
     const uint32_t step = p.step_ptr ? *p.step_ptr : p.step;    // read once, at entry: the Philox counter and the log-prob column
     float* lp = (q.logp != nullptr && step < (uint32_t)q.cols) ? q.logp + (long long)row * q.ld + step : nullptr;
+    int st = 0;                         // the row's automaton state, read once: thread 0 overwrites it behind the __syncthreads() that precede every pick
+    const unsigned* arow = nullptr;
+    if constexpr (GD) {
+        st = guide_state(gd, row);
+        arow = gd.allow + (long long)st * gd.ld_allow;
+    }
     // every wave merges the NCHUNK partials for itself (lane = chunk; the same instructions on the same data: the same bits in all four waves)
     const bool have = lane < NCHUNK;
     const float* pr = q.part + ((long long)row * NCHUNK + (have ? lane : 0)) * 4;
@@ -427,6 +461,7 @@ __device__ __forceinline__ void logp_stage2(const SampleArgs& p, const LogpArgs&
                         const int g = c0 + t * per + i;
                         if (i < per && g < c1 && g != p.suppress) {
                             float v = x[g];
+                            if constexpr (GD) { if (!seen_bit(arow, g)) v = -INFINITY; }
                             if (srow != nullptr && seen_bit(srow, g)) v = penalised(v, e.pen);
                             const float w = expf((v - MT) * invT);
                             ts += w >= min_p ? w : 0.f;
@@ -458,6 +493,7 @@ __device__ __forceinline__ void logp_stage2(const SampleArgs& p, const LogpArgs&
                 w[i] = 0.f;
                 if (ok) {
                     float v = x[g];
+                    if constexpr (GD) { if (!seen_bit(arow, g)) v = -INFINITY; }
                     if (srow != nullptr && seen_bit(srow, g)) v = penalised(v, e.pen);
                     const float wi = expf((v - MT) * invT);
                     w[i] = wi >= min_p ? wi : 0.f;
@@ -492,6 +528,7 @@ __device__ __forceinline__ void logp_stage2(const SampleArgs& p, const LogpArgs&
             p.out[row] = pick;
             if (lp) *lp = x[pick] - lse;
             if constexpr (EX) mark_pick(e, row, pick);
+            if constexpr (GD) guide_advance(gd, row, st, pick);
         }
         return;
     }
@@ -512,6 +549,7 @@ __device__ __forceinline__ void logp_stage2(const SampleArgs& p, const LogpArgs&
             p.out[row] = pick;
             if (lp) *lp = x[pick] - lse;
             if constexpr (EX) mark_pick(e, row, pick);
+            if constexpr (GD) guide_advance(gd, row, st, pick);
         }
         return;
     }
@@ -530,6 +568,7 @@ __device__ __forceinline__ void logp_stage2(const SampleArgs& p, const LogpArgs&
         p.out[row] = sidx[pick];
         if (lp) *lp = sraw[pick] - lse;
         if constexpr (EX) mark_pick(e, row, sidx[pick]);
+        if constexpr (GD) guide_advance(gd, row, st, sidx[pick]);
     }
 }
 
@@ -537,6 +576,8 @@ __global__ __launch_bounds__(NT) void sample_logp_stage1(SampleArgs p, LogpArgs 
 __global__ __launch_bounds__(NT) void sample_logp_stage2(SampleArgs p, LogpArgs q) { logp_stage2<false>(p, q, ExArgs{}); }
 __global__ __launch_bounds__(NT) void sample_ex_stage1(SampleArgs p, LogpArgs q, ExArgs e) { logp_stage1<true>(p, q, e); }
 __global__ __launch_bounds__(NT) void sample_ex_stage2(SampleArgs p, LogpArgs q, ExArgs e) { logp_stage2<true>(p, q, e); }
+__global__ __launch_bounds__(NT) void sample_guided_stage1(SampleArgs p, LogpArgs q, ExArgs e, GuideArgs g) { logp_stage1<true, true>(p, q, e, g); }
+__global__ __launch_bounds__(NT) void sample_guided_stage2(SampleArgs p, LogpArgs q, ExArgs e, GuideArgs g) { logp_stage2<true, true>(p, q, e, g); }
 
 // iadr1_seen_init: one block per sequence zeroes its bitmap row, then ORs in the live tokens of its prompt (left-padded: columns [S - len, S)).
 __global__ __launch_bounds__(NT) void seen_init_kernel(const long long* ids, int S, const int* lengths, int G, int V, unsigned* seen, long long ld_seen) {
@@ -619,6 +660,49 @@ extern "C" int iadr1_sample_ex(const float* logits, long long ld, long long* out
     hipLaunchKernelGGL(sample_ex_stage1, dim3(NCHUNK, B), dim3(NT), 0, stream, p, q, e);
     hipLaunchKernelGGL(sample_ex_stage2, dim3(B), dim3(NT), 0, stream, p, q, e);
     return iadr1_check_launch("sample_ex");
+}
+
+extern "C" long long iadr1_sample_guided_workspace_bytes(int B) { return iadr1_sample_ex_workspace_bytes(B); }
+
+extern "C" int iadr1_sample_guided(const float* logits, long long ld, long long* out, float* logp_out, long long ld_logp, int logp_cols, void* workspace, int B,
+                                   int V, float temperature, int top_k, float top_p, float min_p, float repetition_penalty, unsigned* seen, long long ld_seen,
+                                   int mark_seen, int suppress_token, unsigned long long seed, unsigned step, const unsigned* step_ptr,
+                                   const unsigned long long* seed_ptr, int* state, const unsigned* allow, long long ld_allow, const short* trans,
+                                   long long ld_trans, int S, hipStream_t stream) {
+    IADR1_REQUIRE(allow == nullptr || (state != nullptr && trans != nullptr), "sample_guided: allow needs state [B] and trans [S, ld_trans] beside it (got state %s, trans %s)",
+                  state ? "a buffer" : "NULL", trans ? "a buffer" : "NULL");
+    IADR1_REQUIRE(allow != nullptr || (state == nullptr && trans == nullptr), "sample_guided: state and trans must be NULL when allow is NULL: without the mask there is no automaton to advance");
+    if (allow != nullptr) {
+        IADR1_REQUIRE(S >= 1 && S <= 32767, "sample_guided: S=%d states, outside 1..32767 (trans holds int16)", S);
+        IADR1_REQUIRE(ld_allow >= ((long long)V + 31) / 32, "sample_guided: ld_allow=%lld is less than ceil(V / 32) = %lld", ld_allow, ((long long)V + 31) / 32);
+        IADR1_REQUIRE(ld_trans >= (long long)V, "sample_guided: ld_trans=%lld is less than V = %d", ld_trans, V);
+    }
+    IADR1_REQUIRE(min_p >= 0.f && min_p < 1.f, "sample_guided: min_p must be in [0,1) (got %g)", (double)min_p);
+    IADR1_REQUIRE(repetition_penalty > 0.f && repetition_penalty <= 3.402823466e38f, "sample_guided: repetition_penalty must be finite and > 0 (got %g)", (double)repetition_penalty);
+    IADR1_REQUIRE((repetition_penalty == 1.f && !mark_seen) || (seen != nullptr && ld_seen >= ((long long)V + 31) / 32),
+                  "sample_guided: repetition_penalty != 1 and mark_seen need a seen bitmap [B, ld_seen] with ld_seen >= ceil(V / 32) (got %s, ld_seen %lld, V %d)",
+                  seen ? "a buffer" : "NULL", ld_seen, V);
+    IADR1_REQUIRE(top_p > 0.f && top_p <= 1.f, "sample_guided: top_p must be in (0,1]");
+    IADR1_REQUIRE(top_k > 0 || top_p == 1.f, "sample_guided: top_k <= 0 samples the whole vocabulary and takes top_p = 1 only (got %g): a nucleus over all V tokens is not built", (double)top_p);
+    IADR1_REQUIRE(B > 0 && V > 0 && workspace != nullptr, "sample_guided: empty problem or missing workspace (iadr1_sample_guided_workspace_bytes)");
+    IADR1_REQUIRE(V <= NCHUNK * NT * ITEMS, "sample_guided: V=%d exceeds the built maximum %d", V, NCHUNK * NT * ITEMS);
+    IADR1_REQUIRE(top_k <= MAXK, "sample_guided: top_k=%d exceeds the built maximum %d", top_k, MAXK);
+    IADR1_REQUIRE(logp_out == nullptr || (logp_cols > 0 && ld_logp >= logp_cols), "sample_guided: logp_out needs logp_cols > 0 and ld_logp >= logp_cols");
+    float* cv = (float*)workspace;
+    int* ci = (int*)(cv + (long long)B * NCHUNK * MAXK);
+    float* part = (float*)(ci + (long long)B * NCHUNK * MAXK);
+    SampleArgs p{logits, ld, out, cv, ci, B, V, temperature, top_p, top_k, suppress_token, (uint32_t)seed, (uint32_t)(seed >> 32), step, step_ptr, seed_ptr};
+    LogpArgs q{part, logp_out, ld_logp, logp_cols};
+    ExArgs e{min_p, repetition_penalty, seen, ld_seen, mark_seen != 0};
+    if (allow == nullptr) {     // no guide: iadr1_sample_ex's own kernels, the same device code and the same bits
+        hipLaunchKernelGGL(sample_ex_stage1, dim3(NCHUNK, B), dim3(NT), 0, stream, p, q, e);
+        hipLaunchKernelGGL(sample_ex_stage2, dim3(B), dim3(NT), 0, stream, p, q, e);
+        return iadr1_check_launch("sample_guided");
+    }
+    GuideArgs g{state, allow, trans, ld_allow, ld_trans, S};
+    hipLaunchKernelGGL(sample_guided_stage1, dim3(NCHUNK, B), dim3(NT), 0, stream, p, q, e, g);
+    hipLaunchKernelGGL(sample_guided_stage2, dim3(B), dim3(NT), 0, stream, p, q, e, g);
+    return iadr1_check_launch("sample_guided");
 }
 
 extern "C" int iadr1_seen_init(const long long* ids, int S, const int* lengths, int Bp, int G, int V, unsigned* seen, long long ld_seen, hipStream_t stream) {

@@ -724,6 +724,36 @@ def sample_ex(logits32, temperature, top_k, top_p, seed, step, min_p=0.0, repeti
     return o, logp_out
 
 
+def sample_guided(logits32, temperature, top_k, top_p, seed, step, state=None, allow=None, trans=None, min_p=0.0, repetition_penalty=1.0, seen=None, mark_seen=False,
+                  suppress_token=-1, step_ptr=None, out=None, seed_ptr=None, logp_out=None, want_logp=True):
+    """iadr1_sample_guided: `sample_ex` behind an automaton's allowed-token mask.  state [B] int32 (read and written), allow [S, >= ceil(V / 32)] 32-bit words,
+    trans [S, >= V] int16; tokens whose bit is clear in allow[state[row]] are -inf to the filter, and state[row] <- trans[state[row], pick] after the pick.
+    logp_out keeps sample_logp's meaning (raw logits, no mask).  All three None: bit-equal to sample_ex.  Returns (ids, logp_out or None)."""
+    B, V = logits32.shape
+    o = out if out is not None else torch.empty(B, dtype=torch.int64, device=logits32.device)
+    if logp_out is None and want_logp:
+        assert step_ptr is None and int(step) == 0, "sample_guided: give logp_out [B, cols] when the step (the column) is not 0"
+        logp_out = torch.zeros(B, 1, dtype=F32, device=logits32.device)
+    if seen is not None:
+        assert seen.dim() == 2 and seen.shape[0] == B and seen.element_size() == 4 and seen.stride(1) == 1, "sample_guided: seen is [B, words] of 32-bit words"
+    S = 0
+    if allow is not None:
+        S = allow.shape[0]
+        assert allow.dim() == 2 and allow.element_size() == 4 and allow.stride(1) == 1, "sample_guided: allow is [S, words] of 32-bit words"
+        assert trans is not None and trans.dim() == 2 and trans.dtype == torch.int16 and trans.stride(1) == 1 and trans.shape[0] == S, "sample_guided: trans is [S, >= V] int16"
+        assert state is not None and state.dtype == torch.int32 and state.dim() == 1 and state.numel() == B and state.stride(0) == 1, "sample_guided: state is [B] int32"
+    key = (B, logits32.device)
+    ws = _sample_ex_ws.get(key)     # (iadr1_sample_guided_workspace_bytes == iadr1_sample_ex_workspace_bytes: one buffer serves both)
+    if ws is None:
+        ws = torch.empty(hip.lib().iadr1_sample_guided_workspace_bytes(B), dtype=torch.uint8, device=logits32.device)
+        _sample_ex_ws[key] = ws
+    hip.call("sample_guided", logits32, _ld(logits32), o, logp_out, _ld(logp_out) if logp_out is not None else 0, logp_out.shape[1] if logp_out is not None else 0, ws, B, V,
+             float(temperature), int(top_k), float(top_p), float(min_p), float(repetition_penalty), seen, seen.stride(0) if seen is not None else 0, int(bool(mark_seen)),
+             int(suppress_token), int(seed), int(step), step_ptr, seed_ptr, state, allow, allow.stride(0) if allow is not None else 0, trans,
+             trans.stride(0) if trans is not None else 0, int(S))
+    return o, logp_out
+
+
 def seen_init(ids, lengths, G, V, seen):
     """iadr1_seen_init: seen [Bp * G, >= ceil(V / 32)] 32-bit words <- the live tokens of the left-padded prompts ids [Bp, S] int64 (lengths [Bp] int32, on the
     device), every prompt's row repeated for its G sequences; ids outside [0, V) are ignored."""

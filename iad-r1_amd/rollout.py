@@ -102,9 +102,12 @@ class Rollout:
         self.trace = None           # training arena filled by the decode steps (generate(train_trace=...)); part of the captured graph
         self.decode_events = None   # bench.py sets a list: (start event, end event, decode steps, sum of prompt lengths over sequences) per call
         self.seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.sampling = dict(temperature=0.9, top_k=50, top_p=0.9, suppress=-1, eos=c.eos_token_id, pad=c.pad_token_id, logps=False, min_p=0.0, repetition_penalty=1.0)
+        self.sampling = dict(temperature=0.9, top_k=50, top_p=0.9, suppress=-1, eos=c.eos_token_id, pad=c.pad_token_id, logps=False, min_p=0.0, repetition_penalty=1.0, guided=False)
         self.logps = None           # [N, max_new] fp32 log-probs of the sampled tokens (generate(return_logps=True)): column = the step counter, like out_tokens
         self.seen = None            # [N, ceil(V / 32)] 32-bit words (generate(repetition_penalty != 1)): bit id & 31 of word id >> 5 = the sequence has seen token id
+        # generate(guide=...): the guide.TokenGuide whose tables are on the device, allow [S, ceil(V / 32)] 32-bit words and trans [S, V] int16 (uploaded once per guide
+        # object), and the automaton state of every sequence [N] int32, which the sampler advances inside the captured step
+        self.guide, self.g_allow, self.g_trans, self.g_state = None, None, None, None
 
     # ---- one decode step (graph body) -------------------------------------------------------------------------
     def _decode_step(self):
@@ -173,7 +176,13 @@ class Rollout:
 
     def _sample_and_advance(self):
         s = self.sampling
-        if s["min_p"] != 0.0 or s["repetition_penalty"] != 1.0:
+        if s["guided"]:
+            # iadr1_sample_guided: the mask of every row's automaton state in front of the filters below, the state moved along the pick inside the second launch
+            pen = s["repetition_penalty"] != 1.0
+            ops.sample_guided(self.logits, s["temperature"], s["top_k"], s["top_p"], 0, 0, state=self.g_state, allow=self.g_allow, trans=self.g_trans, min_p=s["min_p"],
+                              repetition_penalty=s["repetition_penalty"], seen=self.seen if pen else None, mark_seen=pen, suppress_token=s["suppress"], step_ptr=self.step,
+                              out=self.sampled, seed_ptr=self.seed_dev, logp_out=self.logps if s["logps"] else None, want_logp=False)
+        elif s["min_p"] != 0.0 or s["repetition_penalty"] != 1.0:
             # iadr1_sample_ex: the penalty reads self.seen and the pick's bit is set inside the sampler's second launch, on this stream, part of the graph
             pen = s["repetition_penalty"] != 1.0
             ops.sample_ex(self.logits, s["temperature"], s["top_k"], s["top_p"], 0, 0, min_p=s["min_p"], repetition_penalty=s["repetition_penalty"], seen=self.seen if pen else None,
@@ -213,7 +222,7 @@ class Rollout:
                 ops.hip.set_decode_cus(0)
 
     def _generate(self, plan: TextPlan, img_embeds, G: int, max_new: int, temperature=0.9, top_k=50, top_p=0.9, seed=0, suppress_eos=False,
-                  stop_at_eos=True, train_carry=None, train_trace=False, shadow=None, return_logps=False, min_p=0.0, repetition_penalty=1.0):
+                  stop_at_eos=True, train_carry=None, train_trace=False, shadow=None, return_logps=False, min_p=0.0, repetition_penalty=1.0, guide=None):
         """plan: the Bp left-padded prompts.  Returns completion ids [Bp*G, max_new] (prompt-major order: p0 x G,
         p1 x G, ...), pad after the first EOS.
         top_k <= 0: the whole vocabulary (top_p must then be 1.0).  return_logps: returns (ids, logps) -- logps [Bp*G, max_new] fp32 on the device, the
@@ -221,6 +230,9 @@ class Rollout:
         min_p, repetition_penalty: trl's GRPOConfig options (iadr1_sample_ex; transformers' order: penalty, temperature, top-k, top-p, min_p).  The penalty is over
         the live prompt tokens (image placeholders included) and the tokens sampled so far, kept as a bitmap on the device (self.seen) that the sampler updates
         inside the captured step.  Greedy decoding honours the penalty and ignores min_p.  The log-probs of return_logps stay unpenalised and unfiltered.
+        guide: a guide.TokenGuide (trl's vllm_guided_decoding_regex) -- every sequence walks the guide's automaton from its start state; tokens the current state does
+        not allow are masked in front of every filter above (iadr1_sample_guided), EOS is allowed exactly where the bytes so far match the pattern, and a sequence cut at
+        max_new is a prefix of a match.  The log-probs of return_logps stay those of the raw row.  suppress_eos is refused beside it: the automaton decides where EOS goes.
         shadow: an overlap.ChunkedRefPass -- the frozen reference's teacher-forced pass over the tokens produced so far is enqueued on ITS stream every
         `shadow.steps` decode steps, behind one event per chunk (the caller reads shadow.logp after shadow.join())."""
         e, c = self.e, self.e.cfg
@@ -239,9 +251,20 @@ class Rollout:
             raise ValueError(f"min_p must be in [0, 1), got {min_p}")
         if not (np.isfinite(repetition_penalty) and repetition_penalty > 0.0):
             raise ValueError(f"repetition_penalty must be finite and > 0, got {repetition_penalty}")
+        if guide is not None:
+            if suppress_eos:
+                raise ValueError("suppress_eos with a guide: the guide's automaton decides where EOS may appear (exactly where the completion matches); drop one of the two")
+            if guide.V != c.vocab_size or guide.eos_id != c.eos_token_id:
+                raise ValueError(f"the guide was built for vocab_size {guide.V} and EOS {guide.eos_id}, the model has {c.vocab_size} and {c.eos_token_id}")
+        if guide is not self.guide:
+            self.guide = guide
+            self.g_allow, self.g_trans = guide.device_tables(dev) if guide is not None else (None, None)
+            if guide is not None and self.g_state is None:
+                self.g_state = torch.zeros(self.N, dtype=torch.int32, device=dev)
+            self.graph = None          # (the tables and the state are kernel arguments of the captured sampler)
         sampling = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p),
                         suppress=c.eos_token_id if suppress_eos else -1, eos=c.eos_token_id if stop_at_eos and not suppress_eos else -1, pad=c.pad_token_id,
-                        logps=bool(return_logps), min_p=min_p, repetition_penalty=repetition_penalty)
+                        logps=bool(return_logps), min_p=min_p, repetition_penalty=repetition_penalty, guided=guide is not None)
         if repetition_penalty != 1.0 and self.seen is None:
             self.seen = torch.zeros(self.N, (c.vocab_size + 31) // 32, dtype=torch.int32, device=dev)
             self.graph = None          # (the buffer is a kernel argument of the captured sampler)
@@ -362,6 +385,8 @@ class Rollout:
         self.out_tokens.fill_(c.pad_token_id)
         if repetition_penalty != 1.0:   # every rollout starts from its prompts' tokens: what the previous one sampled (and a capture's two extra steps) is gone
             ops.seen_init(plan.ids.view(Bp, S), torch.from_numpy(np.asarray(lengths).astype(np.int32)).pin_memory().to(dev, non_blocking=True), G, c.vocab_size, self.seen)
+        if guide is not None:           # every rollout starts from the start state, the token sampled from the prefill's logits included
+            self.g_state.fill_(guide.start)
         self._sample_and_advance()                                           # token 0 from the prefill logits
         # ---- decode ----------------------------------------------------------------------------------------------
         if self.use_graph and self.graph is None:
@@ -370,6 +395,8 @@ class Rollout:
                 state = state + (self.logps,)
             if repetition_penalty != 1.0:
                 state = state + (self.seen,)     # (the warm-up and the capture mark two tokens nobody sampled)
+            if guide is not None:
+                state = state + (self.g_state,)  # (and move the automaton two tokens on)
             saved = [t.clone() for t in state]
             import time as _time
             torch.cuda.synchronize()

@@ -52,6 +52,10 @@ class GRPOArgs:
     # far) are divided by it when positive and multiplied when negative (transformers' RepetitionPenaltyLogitsProcessor).  Greedy rollouts keep it and drop min_p.
     min_p: float | None = 0.0
     repetition_penalty: float = 1.0
+    # a guide.TokenGuide (trl's vllm_guided_decoding_regex, compiled by SCGRPOTrainer) or None: the rollout samples only tokens that keep the completion a prefix
+    # of a match of the pattern, EOS only where it matches (iadr1_sample_guided).  Only which ids get sampled changes: the loss, the rollout's log-probs (raw row,
+    # no mask) and the training arena are what they are without it.  Not with suppress_eos.
+    guide: object | None = None
     # the rollout also returns the log-prob of every token it sampled (temperature 1, unfiltered: the quantity the loss scores); the step's metrics gain
     # rollout/logp_abs_diff_mean, rollout/logp_abs_diff_max and rollout/kl against the policy log-probs of the loss.  Nothing in the loss or the gradients changes.
     rollout_logps: bool = False
@@ -418,6 +422,8 @@ class SCGRPOEngine:
             raise ValueError("GRPOArgs.rollout_is_cap with llava_rotate_right_padded_rows: that path scores a rotated window, whose columns do not line up with the "
                              "rollout's log-probs; set llava_rotate_right_padded_rows=False to weight the completion tokens themselves")
         check_sampler_args("GRPOArgs", args.min_p, args.repetition_penalty)
+        if args.guide is not None and args.suppress_eos:
+            raise ValueError("GRPOArgs.guide with suppress_eos: the guide's automaton decides where EOS may appear; drop one of the two")
         check_reuse_args("GRPOArgs", args.num_iterations, args.epsilon, args.epsilon_high)
         check_objective_args("GRPOArgs", args.loss_type, args.mask_truncated_completions, args.suppress_eos)
         if ref is None and args.beta != 0:
@@ -504,7 +510,7 @@ class SCGRPOEngine:
         toks = self._rollout.generate(plan, img_pol, a.num_generations, a.max_completion_length, temperature=0.0 if greedy else a.temperature,
                                       top_k=a.top_k, top_p=a.top_p, seed=a.seed + 1000003 * self.opt_step + 7919 * self.accum, suppress_eos=a.suppress_eos,
                                       train_carry=train_carry, train_trace=trace, shadow=shadow, return_logps=a.wants_rollout_logps,
-                                      min_p=0.0 if greedy else (a.min_p or 0.0), repetition_penalty=a.repetition_penalty)
+                                      min_p=0.0 if greedy else (a.min_p or 0.0), repetition_penalty=a.repetition_penalty, **({"guide": a.guide} if a.guide is not None else {}))
         self.last_rollout_logps = None
         if a.wants_rollout_logps:
             toks, self.last_rollout_logps = toks

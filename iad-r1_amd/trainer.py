@@ -45,6 +45,9 @@ class GRPOConfig:
     top_p: float = 0.9
     min_p: Optional[float] = 0.0    # trl.GRPOConfig's name: keep the tokens with probability >= min_p x the most likely one's; in [0, 1), None = 0 = off (GRPOArgs.min_p)
     repetition_penalty: float = 1.0     # trl.GRPOConfig's name: transformers' repetition penalty over prompt + completion so far; finite, > 0, 1 = off (GRPOArgs.repetition_penalty)
+    # trl.GRPOConfig's name (there it goes to vLLM's guided decoding): only completions that match the regex can be sampled, EOS exactly where the text matches.
+    # Full match over the UTF-8 bytes in the dialect of guide.compile_regex; compiled once, when the trainer is built, against the processor's tokenizer (GRPOArgs.guide)
+    vllm_guided_decoding_regex: Optional[str] = None
     rollout_logps: bool = False     # log rollout/logp_abs_diff_mean|max and rollout/kl: sampled vs scored log-probs of the rollout's tokens (GRPOArgs.rollout_logps)
     rollout_is_cap: float = 0.0     # > 0 (then >= 1): weight every per-token loss term by min(exp(scored - sampled log-prob), cap); 0 = off (GRPOArgs.rollout_is_cap)
     rollout_is_level: str = "token"     # "token" | "sequence" (one weight per row, from the row's mean log-ratio)
@@ -346,6 +349,13 @@ class SCGRPOTrainer:
         check_reuse_args("GRPOConfig", args.num_iterations, args.epsilon, args.epsilon_high)
         check_sampler_args("GRPOConfig", args.min_p, args.repetition_penalty)
         check_objective_args("GRPOConfig", args.loss_type)
+        guide_dfa = None
+        if args.vllm_guided_decoding_regex is not None:     # a pattern error surfaces here, before any weight is loaded
+            from .guide import compile_regex
+            try:
+                guide_dfa = compile_regex(args.vllm_guided_decoding_regex)
+            except ValueError as err:
+                raise ValueError(f"GRPOConfig.vllm_guided_decoding_regex: {err}") from None
         if args.save_steps and args.save_steps % args.num_iterations != 0:
             raise ValueError(f"GRPOConfig.save_steps ({args.save_steps}) must be a multiple of num_iterations ({args.num_iterations}): a checkpoint holds no cached "
                              "rollout, so a run can only continue from the first optimizer step of a generation")
@@ -409,9 +419,18 @@ class SCGRPOTrainer:
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized():
             group = dist.group.WORLD
+        self.guide = None
+        if guide_dfa is not None:
+            from .guide import TokenGuide, token_bytes
+            t0 = time.perf_counter()
+            self.guide = TokenGuide.build(guide_dfa, token_bytes(getattr(processing_class, "tokenizer", processing_class), self.cfg.vocab_size), self.cfg.eos_token_id,
+                                          self.cfg.vocab_size)
+            if os.environ.get("IADR1_QUIET") != "1":
+                print(f"[iadr1] guided decoding: {self.guide.S} states over {self.guide.V} tokens, tables {self.guide.nbytes / 1e6:.1f} MB, built in "
+                      f"{time.perf_counter() - t0:.2f} s ({guide_dfa.n} byte-level states)", flush=True)
         self.engine = SCGRPOEngine(self.cfg, self.policy, self.ref, GRPOArgs(
             num_generations=args.num_generations, max_prompt_length=args.max_prompt_length, max_completion_length=args.max_completion_length,
-            beta=args.beta, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, min_p=args.min_p, repetition_penalty=args.repetition_penalty, rollout_logps=args.rollout_logps, rollout_is_cap=args.rollout_is_cap, rollout_is_level=args.rollout_is_level,
+            beta=args.beta, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, min_p=args.min_p, repetition_penalty=args.repetition_penalty, guide=self.guide, rollout_logps=args.rollout_logps, rollout_is_cap=args.rollout_is_cap, rollout_is_level=args.rollout_is_level,
             num_iterations=args.num_iterations, epsilon=args.epsilon, epsilon_high=args.epsilon_high, loss_type=args.loss_type, scale_rewards=args.scale_rewards,
             mask_truncated_completions=args.mask_truncated_completions, learning_rate=args.learning_rate, weight_decay=args.weight_decay,
             adam_beta1=args.adam_beta1, adam_beta2=args.adam_beta2, adam_epsilon=args.adam_epsilon, max_grad_norm=args.max_grad_norm,

@@ -384,6 +384,33 @@ int iadr1_sample_ex(const float* logits, long long ld, long long* out, float* lo
                     int V, float temperature, int top_k, float top_p, float min_p, float repetition_penalty, unsigned* seen, long long ld_seen,
                     int mark_seen, int suppress_token, unsigned long long seed, unsigned step, const unsigned* step_ptr,
                     const unsigned long long* seed_ptr, iadr1_stream_t stream);
+/* iadr1_sample_guided: iadr1_sample_ex with an automaton over the vocabulary in front of the filter -- trl's GRPOConfig(vllm_guided_decoding_regex), which the
+ * reference hands to vLLM as a per-step allowed-token mask (REF:trl/trl/trainer/grpo_trainer.py:629,945).  Mask and state live on the device and advance inside
+ * the call, so a captured decode step needs no host in the loop.
+ *   state: [B] int32, read and written; row b is in automaton state state[b], 0 <= state[b] < S (a value outside is clamped into the table, never used as it is).
+ *   allow: [S, ld_allow] 32-bit words, ld_allow >= ceil(V / 32), read only; bit (id & 31) of word (id >> 5) of row s set = token id may follow state s (the
+ *     layout and bit order of `seen`).
+ *   trans: [S, ld_trans] int16, ld_trans >= V, read only; the state after emitting id from s, or -1 where id is not allowed.  1 <= S <= 32767.
+ *   Filter: a token whose bit is clear in allow[state[row]] has filter logit -inf, exactly as suppress_token does, BEFORE the repetition penalty, temperature,
+ *     top-k, top-p and min_p (vLLM's order: the mask is a logits processor; -inf stays -inf through penalty and temperature).  Everything the filter reads is
+ *     masked: the top-k candidates, the greedy argmax, the whole-vocabulary chunk masses and weights.  Ids are bit-equal to iadr1_sample_ex on a copy of the
+ *     logits whose disallowed entries are -inf.
+ *   logp_out: UNCHANGED in meaning -- the temperature-1 log-softmax of the RAW logits at the pick (no mask, no penalty, no filter): an importance weight against
+ *     it keeps correcting the engine mismatch only.
+ *   After the pick, one thread per row does  n = trans[state * ld_trans + pick];  state[row] = n >= 0 ? n : state  (inside stage 2, on the sampler's stream,
+ *     graph-capturable; plain load and store).  The guard matters: when every allowed logit is -inf the sampler's fallbacks may return a disallowed id, and the
+ *     state then stays where it was, in range.  state[row] is read once, at kernel entry, in both launches.
+ *   allow == NULL (state and trans must then be NULL too): iadr1_sample_ex's own kernels are launched -- ids and logp_out bit-equal, nothing else touched.
+ *   Refused on the host, before any launch, one message each (prefix "sample_guided:"): allow without state or trans; state or trans without allow; S outside
+ *     1..32767; ld_allow < ceil(V / 32); ld_trans < V; and everything iadr1_sample_ex refuses.
+ *   Same Philox stream (seed; row, step), step_ptr / seed_ptr, two launches; workspace: iadr1_sample_guided_workspace_bytes(B).  No allocation, no host sync,
+ *     no float atomics: legal under hipGraph capture. */
+long long iadr1_sample_guided_workspace_bytes(int B);
+int iadr1_sample_guided(const float* logits, long long ld, long long* out, float* logp_out, long long ld_logp, int logp_cols, void* workspace, int B,
+                        int V, float temperature, int top_k, float top_p, float min_p, float repetition_penalty, unsigned* seen, long long ld_seen,
+                        int mark_seen, int suppress_token, unsigned long long seed, unsigned step, const unsigned* step_ptr,
+                        const unsigned long long* seed_ptr, int* state, const unsigned* allow, long long ld_allow, const short* trans,
+                        long long ld_trans, int S, iadr1_stream_t stream);
 /* iadr1_seen_init: the seen bitmap of a rollout's Bp * G sequences from its Bp left-padded prompts ids [Bp, S]: zeroes rows [0, Bp * G) (ld_seen words each) and,
  * for sequence r, sets the bits of the lengths[r / G] live tokens of prompt row r / G (columns [S - len, S): image placeholder ids included, left padding
  * not).  Ids outside [0, V) are ignored, never written.  One launch; integer atomic OR on global memory. */

@@ -86,6 +86,9 @@ def build_parser():
                         "The truncation that goes with --top_k 0")
     p.add_argument("--repetition_penalty", type=float, default=1.0,
                    help="rollout sampler: transformers' repetition penalty over the prompt and the completion so far (> 1 discourages repeats); finite and > 0, 1 = off")
+    p.add_argument("--vllm_guided_decoding_regex", type=str, default=None,
+                   help="rollout sampler: only completions that match this regex (full match over the UTF-8 bytes, Python `re` bytes-mode dialect without anchors, "
+                        "look-around, backreferences or flags) can be sampled; EOS is allowed exactly where the text matches. trl's name; unset = off")
     p.add_argument("--rollout_logps", nargs="?", default=False, const=True, type=lambda v: str(v).lower() in ("1", "true", "yes"),
                    help="log rollout/logp_abs_diff_mean|max and rollout/kl: the sampler's log-probs of the tokens it drew against the loss's policy log-probs")
     p.add_argument("--rollout_is_cap", type=float, default=0.0,

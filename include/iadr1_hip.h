@@ -272,7 +272,8 @@ int iadr1_dlogits_rows(const float* logits, long long ld, const long long* targe
  * without the [M, V] logits reaching HBM: the GEMM's epilogue reduces every 64-column slice to (max, sum exp) and picks the target logit, a second launch
  * merges the slices in a fixed order (deterministic).  `workspace`: iadr1_linear_logprob_workspace_bytes(M, V) bytes, caller-owned, 8-byte aligned.
  * iadr1_linear_logprob_dlogits: the backward's first half -- the logits are recomputed and leave as dl[M, V] = g[r] * (onehot(target) - exp(x - lse[r])) in bf16
- * (the arithmetic of iadr1_dlogits_rows); dH = dl . W and dW += dl^T . H are iadr1_gemm_nt_bf16 calls.  K, ldh, ldw multiples of 8, ldd multiple of 8. */
+ * (the arithmetic of iadr1_dlogits_rows); dH = dl . W and dW += dl^T . H are iadr1_gemm_nt_bf16 calls.  K, ldh, ldw multiples of 8.  ldd: any value >= V; with ldd a
+ * multiple of 8 and dl 16-byte aligned the rows leave as 16-byte stores (the hot path), otherwise element by element. */
 long long iadr1_linear_logprob_workspace_bytes(int M, int V);
 int iadr1_linear_logprob_fwd(const void* H, const void* W, const long long* targets, float* logp, float* lse, void* workspace, int M, int V, int K,
                              long long ldh, long long ldw, iadr1_stream_t stream);

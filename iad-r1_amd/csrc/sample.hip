@@ -1,16 +1,22 @@
 // Fused sampler for the group rollout (gfx950): temperature -> top-k -> top-p -> multinomial over fp32
-// logits [B, V].  Same filter semantics as the sampler the reference drives
-// (vLLM SamplingParams(temperature, top_p=0.9, top_k=50), /root/reference/train/stage_rl/trainer/
-// sc_grpo_trainer.py:353-358): top-p is evaluated on the top-k-renormalised distribution and always keeps the
-// most likely token.  Randomness is a counter-based Philox4x32-10 stream keyed by (seed; row, step), so
-// token ids are reproducible run-to-run and checkable on the CPU.  temperature == 0 selects greedy argmax
-// (lowest index wins ties), the mode used for bit-exact parity against the oracle.
+// logits [B, V].  Same filter semantics as the sampler the reference drives (vLLM SamplingParams(temperature,
+// top_p=0.9, top_k=50), its train/stage_rl/trainer/sc_grpo_trainer.py:353-358): top-p is evaluated on the
+// top-k-renormalised distribution and always keeps the most likely token.  Randomness is a counter-based
+// Philox4x32-10 stream keyed by (seed; row, step), so token ids are reproducible run-to-run and checkable on the
+// CPU.  temperature == 0 selects greedy argmax (lowest index wins ties), the mode used for bit-exact parity
+// against the oracle.
 //
 // HBM/L2-bound selection problem, two launches so that a 64-row batch still fills the chip:
 //   stage 1: grid (NCHUNK, B): each block reads its slice of the row ONCE into registers and extracts its local
 //            top-K with an exact radix select (11+11+10 bits, LDS histograms) + index-ordered compaction;
 //   stage 2: grid (B): the NCHUNK*K survivors -> exact global top-K (same routine) -> rank sort -> softmax,
 //            top-p cut, inverse-CDF draw.
+//
+// ONE body per stage, stage1<LP, EX, GD> and stage2<LP, EX, GD>, behind all four entry points; a flag that is off compiles its code out:
+//   LP  the log-prob of the pick + whole-vocabulary sampling for top_k <= 0     iadr1_sample_topk_topp: sample_stage1/2 <0, 0, 0>; iadr1_sample_logp: sample_logp_stage1/2 <1, 0, 0>
+//   EX  a repetition penalty in front of the filter and a min_p cut behind it   iadr1_sample_ex: sample_ex_stage1/2 <1, 1, 0>
+//   GD  a per-row automaton's mask in front of everything the filter does       iadr1_sample_guided: sample_guided_stage1/2 <1, 1, 1>; without a guide sample_ex's pair
+// The ids of two entry points are bit-equal wherever the newer one's additions are neutral, because they are this code.  The host side is one function too.
 #include "common.h"
 
 namespace {
@@ -163,11 +169,32 @@ __device__ __forceinline__ int eff_k(const SampleArgs& p) {
     return min(min(p.top_k > 0 ? p.top_k : MAXK, MAXK), p.V);
 }
 
-// The single-thread tail of stage 2: softmax over the n rank-sorted candidates in sval (weights left in w), top-p cut, inverse-CDF draw.  Returns the
-// RANK of the pick.  One function for both stage-2 kernels: iadr1_sample_logp's ids are bit-equal to iadr1_sample_topk_topp's because they are this code.
-// min_p (iadr1_sample_ex; 0 from the two older entry points, where the compare folds away): a further cut of the same rank-ordered prefix -- w[0] is 1, so
-// "w[j] >= min_p" is transformers' MinPLogitsWarper relative to the most likely token, and the shorter of the two prefixes wins.
-__device__ __forceinline__ int topk_topp_pick(const SampleArgs& p, int row, const float* sval, float* w, int n, float min_p = 0.f) {
+// The row is cut into NCHUNK chunks of csize ids; inside a chunk thread t owns the CONTIGUOUS ids g0 + i, i < per <= ITEMS, so that id order == (thread, item)
+// order.  Stage 1 loads its slice by this; the whole-vocabulary draw of stage 2 reads slices again by the same assignment.
+struct Slice {
+    int g0, per, c1;
+    __device__ __forceinline__ bool has(int i) const { return i < per && g0 + i < c1; }
+};
+struct Slices {
+    int V, csize, per;
+    __device__ __forceinline__ explicit Slices(int V_) : V(V_), csize((V_ + NCHUNK - 1) / NCHUNK), per((csize + NT - 1) / NT) {}
+    __device__ __forceinline__ Slice of(int chunk) const {
+        const int c0 = chunk * csize, c1 = min(V, c0 + csize);
+        return Slice{c0 + (int)threadIdx.x * per, per, c1};
+    }
+};
+
+// The uniform of (seed; row, step).  The step is the Philox counter and, with LP, the log-prob column.
+__device__ __forceinline__ uint32_t read_step(const SampleArgs& p) { return p.step_ptr ? *p.step_ptr : p.step; }
+__device__ __forceinline__ float draw_uniform(const SampleArgs& p, int row, uint32_t step) {
+    const unsigned long long sd = p.seed_ptr ? *p.seed_ptr : (((unsigned long long)p.seed_hi << 32) | p.seed_lo);
+    return philox_uniform((uint32_t)sd, (uint32_t)(sd >> 32), (uint32_t)row, step);
+}
+
+// The single-thread tail of stage 2: softmax over the n rank-sorted candidates in sval (weights left in w), top-p cut, inverse-CDF draw.  Returns the RANK of
+// the pick.  It reads the step for itself, in thread 0, where the plain pair has always read it.  min_p (EX; 0 otherwise, where the compare folds away): a further
+// cut of the same rank-ordered prefix -- w[0] is 1, so "w[j] >= min_p" is transformers' MinPLogitsWarper relative to the most likely token; the shorter prefix wins.
+__device__ __forceinline__ int topk_topp_pick(const SampleArgs& p, int row, const float* sval, float* w, int n, float min_p) {
     const float invT = 1.f / p.temperature;
     const float mx = sval[0] * invT;
     float tot = 0.f;
@@ -181,9 +208,7 @@ __device__ __forceinline__ int topk_topp_pick(const SampleArgs& p, int row, cons
         before += w[j];
         ++nk;
     }
-    const uint32_t step = p.step_ptr ? *p.step_ptr : p.step;
-    const unsigned long long sd = p.seed_ptr ? *p.seed_ptr : (((unsigned long long)p.seed_hi << 32) | p.seed_lo);
-    const float u = philox_uniform((uint32_t)sd, (uint32_t)(sd >> 32), (uint32_t)row, step) * kept;
+    const float u = draw_uniform(p, row, read_step(p)) * kept;
     float cum = 0.f;
     int pick = nk - 1;
     for (int j = 0; j < nk; ++j) {
@@ -193,72 +218,7 @@ __device__ __forceinline__ int topk_topp_pick(const SampleArgs& p, int row, cons
     return pick;
 }
 
-__global__ __launch_bounds__(NT) void sample_stage1(SampleArgs p) {
-    __shared__ int hist[2048];
-    __shared__ int sh_i[8];
-    __shared__ float oval[MAXK];
-    __shared__ int oidx[MAXK];
-    const int row = blockIdx.y, chunk = blockIdx.x, t = threadIdx.x;
-    const float* x = p.logits + (long long)row * p.ld;
-    const int csize = (p.V + NCHUNK - 1) / NCHUNK;
-    const int per = (csize + NT - 1) / NT;  // <= ITEMS
-    const int c0 = chunk * csize, c1 = min(p.V, c0 + csize);
-    float val[ITEMS];
-    int idx[ITEMS];
-#pragma unroll
-    for (int i = 0; i < ITEMS; ++i) {
-        const int g = c0 + t * per + i;
-        const bool ok = i < per && g < c1;
-        idx[i] = ok ? g : -1;
-        val[i] = ok ? (g == p.suppress ? -INFINITY : x[g]) : -INFINITY;
-    }
-    const int K = eff_k(p);
-    const int n = block_topk<ITEMS>(val, idx, K, hist, sh_i, oval, oidx);
-    float* cv = p.cand_val + ((long long)row * NCHUNK + chunk) * MAXK;
-    int* ci = p.cand_idx + ((long long)row * NCHUNK + chunk) * MAXK;
-    if (t < MAXK) {
-        cv[t] = t < n ? oval[t] : -INFINITY;
-        ci[t] = t < n ? oidx[t] : -1;
-    }
-}
-
-__global__ __launch_bounds__(NT) void sample_stage2(SampleArgs p) {
-    __shared__ int hist[2048];
-    __shared__ int sh_i[8];
-    __shared__ float cval[MAXK];
-    __shared__ int cidx[MAXK];
-    __shared__ float sval[MAXK];
-    __shared__ int sidx[MAXK];
-    constexpr int NI = NCHUNK * MAXK / NT;  // 8 candidates per thread, contiguous => global index order is preserved
-    const int row = blockIdx.x, t = threadIdx.x;
-    const float* cv = p.cand_val + (long long)row * NCHUNK * MAXK;
-    const int* ci = p.cand_idx + (long long)row * NCHUNK * MAXK;
-    float val[NI];
-    int idx[NI];
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        idx[i] = ci[t * NI + i];
-        val[i] = cv[t * NI + i];
-    }
-    const int K = eff_k(p);
-    const int n = block_topk<NI>(val, idx, K, hist, sh_i, cval, cidx);
-    if (p.temperature <= 0.f) {
-        if (t == 0) p.out[row] = n > 0 ? cidx[0] : 0;
-        return;
-    }
-    if (t < n) {
-        const float v = cval[t];
-        const int id = cidx[t];
-        int rank = 0;
-        for (int j = 0; j < n; ++j) rank += (cval[j] > v) || (cval[j] == v && cidx[j] < id);
-        sval[rank] = v;
-        sidx[rank] = id;
-    }
-    __syncthreads();
-    if (t == 0) p.out[row] = sidx[topk_topp_pick(p, row, sval, cval, n)];
-}
-
-// ---- iadr1_sample_logp: the same sampler + whole-vocabulary sampling (top_k <= 0) + the log-prob of the pick ------------------------------------
+// ---- LP: whole-vocabulary sampling (top_k <= 0) + the log-prob of the pick ----------------------------------------------------------------------
 // Both need the softmax normaliser of the WHOLE row.  Stage 1 holds its slice in registers anyway: it also reduces it to
 //   (m1, s1) = (max x, sum exp(x - m1))                 temperature 1, nothing filtered or suppressed: what the loss scores (iadr1_logprob_rows)
 //   (mT, sT) = (max x, sum exp((x - mT) / T))           suppressed token excluded; only for top_k <= 0
@@ -267,6 +227,7 @@ __global__ __launch_bounds__(NT) void sample_stage2(SampleArgs p) {
 // exclusive block scan of the per-thread sums (thread t owns contiguous ids, as in stage 1) finds the id.  Summation tree of a weight, all fixed:
 // <= ITEMS serial adds in the thread, 6 shuffle levels in the wave, 3 adds over the waves (stage 1: the chunk mass; stage 2 again: the position in
 // the chunk), 6 shuffle levels over the chunks: at most 2 * (20 + 6 + 3) + 6 = 64 fp32 additions deep.
+// top_k <= 0 means "MAXK candidates" without LP (eff_k) and the whole vocabulary with it: every use of whole_vocab() sits behind `if constexpr (LP)`.
 struct LogpArgs {
     float* part;        // scratch [B][NCHUNK][4]: m1, s1, mT, sT
     float* logp;        // optional [B, ld] log-probs, column = the step value
@@ -276,9 +237,8 @@ struct LogpArgs {
 
 __device__ __forceinline__ bool whole_vocab(const SampleArgs& p) { return p.top_k <= 0 && p.temperature > 0.f; }
 
-// ---- iadr1_sample_ex: the same two kernels with a repetition penalty in front of the filter and a min_p cut behind it ----------------------------------
-// Both kernel bodies are templates on EX; iadr1_sample_logp launches the EX = false instantiations, in which none of the code below exists.  With EX the
-// filter sees x' (transformers' RepetitionPenaltyLogitsProcessor over the ids whose bit is set in `seen`), the log-prob keeps seeing the raw x.
+// ---- EX: a repetition penalty in front of the filter and a min_p cut behind it -------------------------------------------------------------------------
+// The filter sees x' (transformers' RepetitionPenaltyLogitsProcessor over the ids whose bit is set in `seen`), the log-prob keeps seeing the raw x.
 // Whole vocabulary with min_p > 0: whether a token is kept depends on the maximum of the WHOLE row, which stage 1 does not have, so stage 2 forms the
 // thresholded chunk masses itself (the block reads the row once more, chunk by chunk, with stage 1's thread -> id assignment and a tree no deeper than
 // stage 1's); stage 1 contributes the maxima and (m1, s1).
@@ -300,10 +260,10 @@ __device__ __forceinline__ void mark_pick(const ExArgs& e, int row, int pick) { 
     if (e.mark) e.seen[(long long)row * e.ld_seen + (pick >> 5)] |= 1u << (pick & 31);
 }
 
-// ---- iadr1_sample_guided: the same two kernels with a per-row automaton in front of everything the filter does --------------------------------------------------
-// One more template flag, GD; the four kernels above launch the GD = false instantiations, in which none of the code below exists.  Row b is in state[b]; the
-// filter sees -inf wherever bit id of allow[state[b]] is clear (before the penalty: -inf stays -inf through it and through the temperature), the log-prob keeps
-// seeing the raw x.  The state is read once, at entry, into a register in both stages; stage 2's thread 0 moves it along trans after the pick.
+// ---- GD: a per-row automaton in front of everything the filter does -----------------------------------------------------------------------------------------------
+// Row b is in state[b]; the filter sees -inf wherever bit id of allow[state[b]] is clear (before the penalty: -inf stays -inf through it and through the
+// temperature), the log-prob keeps seeing the raw x.  The state is read once, at entry, into a register in both stages; stage 2's thread 0 moves it along trans
+// after the pick.
 struct GuideArgs {
     int* state;             // [B], 0 <= state[b] < S
     const unsigned* allow;  // [S, ld_allow] bitmap, bit id & 31 of word id >> 5 (the layout of `seen`)
@@ -329,79 +289,78 @@ __device__ __forceinline__ float wave_incscan(float v) {
     return v;
 }
 
-template <bool EX, bool GD = false>
-__device__ __forceinline__ void logp_stage1(const SampleArgs& p, const LogpArgs& q, const ExArgs& e, const GuideArgs& gd = GuideArgs{}) {
+template <bool LP, bool EX, bool GD>     // EX and GD build on LP: the four combinations of the header are the ones that exist
+__device__ __forceinline__ void stage1(const SampleArgs& p, const LogpArgs& q, const ExArgs& e, const GuideArgs& gd) {
     __shared__ int hist[2048];
     __shared__ int sh_i[8];
     __shared__ float sh_f[16];
     __shared__ float oval[MAXK];
     __shared__ int oidx[MAXK];
     const int row = blockIdx.y, chunk = blockIdx.x, t = threadIdx.x;
-    const float* x = p.logits + (long long)row * p.ld;
-    const int csize = (p.V + NCHUNK - 1) / NCHUNK;
-    const int per = (csize + NT - 1) / NT;  // <= ITEMS
-    const int c0 = chunk * csize, c1 = min(p.V, c0 + csize);
     float val[ITEMS];
     int idx[ITEMS];
+    const float* x = p.logits + (long long)row * p.ld;
+    const Slice sl = Slices(p.V).of(chunk);
     float xs = -INFINITY;   // the suppressed token's own logit, if this thread holds it: it counts at temperature 1
 #pragma unroll
     for (int i = 0; i < ITEMS; ++i) {
-        const int g = c0 + t * per + i;
-        const bool ok = i < per && g < c1;
+        const int g = sl.g0 + i;
+        const bool ok = sl.has(i);
         idx[i] = ok ? g : -1;
         const float v = ok ? x[g] : -INFINITY;
         const bool sup = ok && g == p.suppress;
         if (sup) xs = v;
         val[i] = sup ? -INFINITY : v;
     }
-    const bool wv = whole_vocab(p);
-    float mT = -INFINITY;
+    if constexpr (LP) {
+        const bool wv = whole_vocab(p);
+        float mT = -INFINITY;
 #pragma unroll
-    for (int i = 0; i < ITEMS; ++i) mT = fmaxf(mT, val[i]);
-    const float m1 = block_max<NT>(fmaxf(mT, xs), sh_f);
-    float s1 = 0.f, sT = 0.f;
-    if (m1 > -INFINITY) {
+        for (int i = 0; i < ITEMS; ++i) mT = fmaxf(mT, val[i]);
+        const float m1 = block_max<NT>(fmaxf(mT, xs), sh_f);
+        float s1 = 0.f, sT = 0.f;
+        if (m1 > -INFINITY) {
 #pragma unroll
-        for (int i = 0; i < ITEMS; ++i) s1 += expf(val[i] - m1);      // (padding and the suppressed slot hold -inf: they add 0)
-        if (xs > -INFINITY) s1 += expf(xs - m1);
-    }
-    if constexpr (GD) {
-        // (m1, s1) above are the raw row's; the automaton's mask comes first of all the filter does
-        const unsigned* arow = gd.allow + (long long)guide_state(gd, row) * gd.ld_allow;
-        mT = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < ITEMS; ++i) {
-            if (idx[i] >= 0 && !seen_bit(arow, idx[i])) val[i] = -INFINITY;
-            mT = fmaxf(mT, val[i]);
+            for (int i = 0; i < ITEMS; ++i) s1 += expf(val[i] - m1);      // (padding and the suppressed slot hold -inf: they add 0)
+            if (xs > -INFINITY) s1 += expf(xs - m1);
         }
-    }
-    if constexpr (EX) {
-        // (m1, s1) above are the raw row's; from here on val holds x' (-inf stays -inf: the suppressed slot and the padding need no test)
-        if (e.pen != 1.f) {
-            const unsigned* srow = e.seen + (long long)row * e.ld_seen;
+        if constexpr (GD) {
+            // (m1, s1) above are the raw row's; the automaton's mask comes first of all the filter does
+            const unsigned* arow = gd.allow + (long long)guide_state(gd, row) * gd.ld_allow;
             mT = -INFINITY;
 #pragma unroll
             for (int i = 0; i < ITEMS; ++i) {
-                if (idx[i] >= 0 && seen_bit(srow, idx[i])) val[i] = penalised(val[i], e.pen);
+                if (idx[i] >= 0 && !seen_bit(arow, idx[i])) val[i] = -INFINITY;
                 mT = fmaxf(mT, val[i]);
             }
         }
-    }
-    mT = block_max<NT>(mT, sh_f + 4);
-    const float invT = wv ? 1.f / p.temperature : 0.f;
-    if (wv && mT > -INFINITY) {
+        if constexpr (EX) {
+            // (m1, s1) above are the raw row's; from here on val holds x' (-inf stays -inf: the suppressed slot and the padding need no test)
+            if (e.pen != 1.f) {
+                const unsigned* srow = e.seen + (long long)row * e.ld_seen;
+                mT = -INFINITY;
 #pragma unroll
-        for (int i = 0; i < ITEMS; ++i) sT += expf((val[i] - mT) * invT);
+                for (int i = 0; i < ITEMS; ++i) {
+                    if (idx[i] >= 0 && seen_bit(srow, idx[i])) val[i] = penalised(val[i], e.pen);
+                    mT = fmaxf(mT, val[i]);
+                }
+            }
+        }
+        mT = block_max<NT>(mT, sh_f + 4);
+        const float invT = wv ? 1.f / p.temperature : 0.f;
+        if (wv && mT > -INFINITY) {
+#pragma unroll
+            for (int i = 0; i < ITEMS; ++i) sT += expf((val[i] - mT) * invT);
+        }
+        s1 = block_sum<NT>(s1, sh_f + 8);
+        sT = block_sum<NT>(sT, sh_f + 12);
+        if (t == 0) {
+            float* o = q.part + ((long long)row * NCHUNK + chunk) * 4;
+            o[0] = m1; o[1] = s1; o[2] = mT; o[3] = sT;
+        }
+        if (wv) return;     // no candidate lists: stage 2 draws from the chunk masses
     }
-    s1 = block_sum<NT>(s1, sh_f + 8);
-    sT = block_sum<NT>(sT, sh_f + 12);
-    if (t == 0) {
-        float* o = q.part + ((long long)row * NCHUNK + chunk) * 4;
-        o[0] = m1; o[1] = s1; o[2] = mT; o[3] = sT;
-    }
-    if (wv) return;     // no candidate lists: stage 2 draws from the chunk masses
-    const int K = eff_k(p);
-    const int n = block_topk<ITEMS>(val, idx, K, hist, sh_i, oval, oidx);
+    const int n = block_topk<ITEMS>(val, idx, eff_k(p), hist, sh_i, oval, oidx);
     float* cv = p.cand_val + ((long long)row * NCHUNK + chunk) * MAXK;
     int* ci = p.cand_idx + ((long long)row * NCHUNK + chunk) * MAXK;
     if (t < MAXK) {
@@ -410,8 +369,16 @@ __device__ __forceinline__ void logp_stage1(const SampleArgs& p, const LogpArgs&
     }
 }
 
-template <bool EX, bool GD = false>
-__device__ __forceinline__ void logp_stage2(const SampleArgs& p, const LogpArgs& q, const ExArgs& e, const GuideArgs& gd = GuideArgs{}) {
+template <bool LP, bool EX, bool GD>
+__device__ __forceinline__ void commit_pick(const SampleArgs& p, const ExArgs& e, const GuideArgs& gd, int row, int st, int pick, float* lp, const float* raw, float lse) {
+    p.out[row] = pick;
+    if constexpr (LP) { if (lp) *lp = *raw - lse; }
+    if constexpr (EX) mark_pick(e, row, pick);
+    if constexpr (GD) guide_advance(gd, row, st, pick);
+}
+
+template <bool LP, bool EX, bool GD>
+__device__ __forceinline__ void stage2(const SampleArgs& p, const LogpArgs& q, const ExArgs& e, const GuideArgs& gd) {
     __shared__ int hist[2048];
     __shared__ int sh_i[8];
     __shared__ float sh_f[8];
@@ -420,117 +387,107 @@ __device__ __forceinline__ void logp_stage2(const SampleArgs& p, const LogpArgs&
     __shared__ float sval[MAXK];
     __shared__ int sidx[MAXK];
     __shared__ float sraw[MAXK];
-    constexpr int NI = NCHUNK * MAXK / NT;
+    constexpr int NI = NCHUNK * MAXK / NT;  // 8 candidates per thread
     const int row = blockIdx.x, t = threadIdx.x, lane = t & 63;
-    const float* x = p.logits + (long long)row * p.ld;
-    const uint32_t step = p.step_ptr ? *p.step_ptr : p.step;    // read once, at entry: the Philox counter and the log-prob column
-    float* lp = (q.logp != nullptr && step < (uint32_t)q.cols) ? q.logp + (long long)row * q.ld + step : nullptr;
+    const float* x = p.logits + (long long)row * p.ld;     // read with LP only: the log-prob's raw logit and the whole-vocabulary draw
+    const uint32_t step = read_step(p);     // read once, at entry: the Philox counter of the whole-vocabulary draw and the log-prob column
+    float* lp = (LP && q.logp != nullptr && step < (uint32_t)q.cols) ? q.logp + (long long)row * q.ld + step : nullptr;
+    float lse = 0.f;    // the raw row's log-sum-exp at temperature 1 (LP)
     int st = 0;                         // the row's automaton state, read once: thread 0 overwrites it behind the __syncthreads() that precede every pick
     const unsigned* arow = nullptr;
     if constexpr (GD) {
         st = guide_state(gd, row);
         arow = gd.allow + (long long)st * gd.ld_allow;
     }
-    // every wave merges the NCHUNK partials for itself (lane = chunk; the same instructions on the same data: the same bits in all four waves)
-    const bool have = lane < NCHUNK;
-    const float* pr = q.part + ((long long)row * NCHUNK + (have ? lane : 0)) * 4;
-    const float m1 = have ? pr[0] : -INFINITY, s1 = have ? pr[1] : 0.f;
-    const float M1 = wave_max(m1);
-    const float lse = M1 + logf(wave_sum(m1 > -INFINITY ? s1 * expf(m1 - M1) : 0.f));
-    if (whole_vocab(p)) {
-        const float invT = 1.f / p.temperature;
-        const float mT = have ? pr[2] : -INFINITY, sT = have ? pr[3] : 0.f;
-        const float MT = wave_max(mT);
-        float mass = mT > -INFINITY ? sT * expf((mT - MT) * invT) : 0.f;
-        const int csize = (p.V + NCHUNK - 1) / NCHUNK;
-        const int per = (csize + NT - 1) / NT;
-        const unsigned* srow = nullptr;
-        float min_p = 0.f;
-        if constexpr (EX) {
-            if (e.pen != 1.f) srow = e.seen + (long long)row * e.ld_seen;
-            min_p = e.min_p;
-            if (min_p > 0.f) {
-                // the kept set hangs on MT: the chunk masses over the tokens with exp((x' - MT) / T) >= min_p, formed here.  Per chunk: <= ITEMS serial adds in
-                // the thread, 6 shuffle levels, 3 adds over the waves -- stage 1's depth; lane c of every wave ends up with chunk c's mass, the same bits in all four.
-                __shared__ float cm[NCHUNK][NT / WAVE];
-                for (int c = 0; c < NCHUNK; ++c) {
-                    const int c0 = c * csize, c1 = min(p.V, c0 + csize);
-                    float ts = 0.f;
-#pragma unroll
-                    for (int i = 0; i < ITEMS; ++i) {
-                        const int g = c0 + t * per + i;
-                        if (i < per && g < c1 && g != p.suppress) {
-                            float v = x[g];
-                            if constexpr (GD) { if (!seen_bit(arow, g)) v = -INFINITY; }
-                            if (srow != nullptr && seen_bit(srow, g)) v = penalised(v, e.pen);
-                            const float w = expf((v - MT) * invT);
-                            ts += w >= min_p ? w : 0.f;
-                        }
-                    }
-                    ts = wave_sum(ts);
-                    if (lane == 0) cm[c][t >> 6] = ts;
-                }
-                __syncthreads();
-                mass = have ? ((cm[lane][0] + cm[lane][1]) + cm[lane][2]) + cm[lane][3] : 0.f;
-            }
-        }
-        const float inc = wave_incscan(mass);
-        const float total = __shfl(inc, NCHUNK - 1, WAVE);
-        const unsigned long long sd = p.seed_ptr ? *p.seed_ptr : (((unsigned long long)p.seed_hi << 32) | p.seed_lo);
-        const float target = philox_uniform((uint32_t)sd, (uint32_t)(sd >> 32), (uint32_t)row, step) * total;
-        // first chunk whose inclusive mass exceeds the target; rounding may leave none: then the last chunk that has any mass
-        const unsigned long long hit = __ballot(have && inc > target), any = __ballot(have && mass > 0.f);
-        const int chunk = hit ? (int)__builtin_ctzll(hit) : (any ? 63 - (int)__builtin_clzll(any) : 0);
-        const float rest = target - (__shfl(inc, chunk, WAVE) - __shfl(mass, chunk, WAVE));     // what is left of the target inside the chunk
-        const int c0 = chunk * csize, c1 = min(p.V, c0 + csize);
-        float w[ITEMS];
-        float ts = 0.f;
-#pragma unroll
-        for (int i = 0; i < ITEMS; ++i) {
-            const int g = c0 + t * per + i;
-            const bool ok = i < per && g < c1 && g != p.suppress;      // (g < c1 <= V: the re-read stays inside the row)
+    if constexpr (LP) {
+        // every wave merges the NCHUNK partials for itself (lane = chunk; the same instructions on the same data: the same bits in all four waves)
+        const bool have = lane < NCHUNK;
+        const float* pr = q.part + ((long long)row * NCHUNK + (have ? lane : 0)) * 4;
+        const float m1 = have ? pr[0] : -INFINITY, s1 = have ? pr[1] : 0.f;
+        const float M1 = wave_max(m1);
+        lse = M1 + logf(wave_sum(m1 > -INFINITY ? s1 * expf(m1 - M1) : 0.f));
+        if (whole_vocab(p)) {
+            const float invT = 1.f / p.temperature;
+            const float mT = have ? pr[2] : -INFINITY, sT = have ? pr[3] : 0.f;
+            const float MT = wave_max(mT);
+            float mass = mT > -INFINITY ? sT * expf((mT - MT) * invT) : 0.f;
+            const Slices slices(p.V);
+            const unsigned* srow = nullptr;
+            float min_p = 0.f;
+            // what the filter leaves of token g.  The order is the contract with transformers' processors: the automaton's mask, the penalty, the temperature,
+            // then the min_p cut relative to the row maximum (its weight is 1)
+            auto weight = [&](int g) {
+                float v = x[g];
+                if constexpr (GD) { if (!seen_bit(arow, g)) v = -INFINITY; }
+                if constexpr (EX) { if (srow != nullptr && seen_bit(srow, g)) v = penalised(v, e.pen); }
+                const float w = expf((v - MT) * invT);
+                return (!EX || w >= min_p) ? w : 0.f;
+            };
             if constexpr (EX) {
-                w[i] = 0.f;
-                if (ok) {
-                    float v = x[g];
-                    if constexpr (GD) { if (!seen_bit(arow, g)) v = -INFINITY; }
-                    if (srow != nullptr && seen_bit(srow, g)) v = penalised(v, e.pen);
-                    const float wi = expf((v - MT) * invT);
-                    w[i] = wi >= min_p ? wi : 0.f;
-                }
-            } else {
-                w[i] = ok ? expf((x[g] - MT) * invT) : 0.f;
-            }
-            ts += w[i];
-        }
-        // exclusive block scan of the thread sums, in id order
-        const float winc = wave_incscan(ts);
-        if (t == 0) { sh_i[0] = 0x7fffffff; sh_i[1] = -1; }
-        if (lane == 63) sh_f[t >> 6] = winc;
-        __syncthreads();
-        float cum = winc - ts;
-        for (int i = 0; i < (t >> 6); ++i) cum += sh_f[i];
-        int first = 0x7fffffff, last = -1;      // first id whose inclusive weight exceeds `rest`; last id of the chunk with any weight (rounding fallback)
+                if (e.pen != 1.f) srow = e.seen + (long long)row * e.ld_seen;
+                min_p = e.min_p;
+                if (min_p > 0.f) {
+                    // the kept set hangs on MT: the chunk masses over the tokens with exp((x' - MT) / T) >= min_p, formed here.  Per chunk: <= ITEMS serial adds in
+                    // the thread, 6 shuffle levels, 3 adds over the waves -- stage 1's depth; lane c of every wave ends up with chunk c's mass, the same bits in all four.
+                    __shared__ float cm[NCHUNK][NT / WAVE];
+                    for (int c = 0; c < NCHUNK; ++c) {
+                        const Slice sl = slices.of(c);
+                        float ts = 0.f;
 #pragma unroll
-        for (int i = 0; i < ITEMS; ++i) {
-            cum += w[i];
-            if (w[i] > 0.f) {
-                const int g = c0 + t * per + i;
-                last = g;
-                if (cum > rest && first == 0x7fffffff) first = g;
+                        for (int i = 0; i < ITEMS; ++i) {
+                            const int g = sl.g0 + i;
+                            if (sl.has(i) && g != p.suppress) ts += weight(g);
+                        }
+                        ts = wave_sum(ts);
+                        if (lane == 0) cm[c][t >> 6] = ts;
+                    }
+                    __syncthreads();
+                    mass = have ? ((cm[lane][0] + cm[lane][1]) + cm[lane][2]) + cm[lane][3] : 0.f;
+                }
             }
+            const float inc = wave_incscan(mass);
+            const float total = __shfl(inc, NCHUNK - 1, WAVE);
+            const float target = draw_uniform(p, row, step) * total;
+            // first chunk whose inclusive mass exceeds the target; rounding may leave none: then the last chunk that has any mass
+            const unsigned long long hit = __ballot(have && inc > target), any = __ballot(have && mass > 0.f);
+            const int chunk = hit ? (int)__builtin_ctzll(hit) : (any ? 63 - (int)__builtin_clzll(any) : 0);
+            const float rest = target - (__shfl(inc, chunk, WAVE) - __shfl(mass, chunk, WAVE));     // what is left of the target inside the chunk
+            const Slice sl = slices.of(chunk);
+            float w[ITEMS];
+            float ts = 0.f;
+#pragma unroll
+            for (int i = 0; i < ITEMS; ++i) {
+                const int g = sl.g0 + i;
+                w[i] = 0.f;
+                if (sl.has(i) && g != p.suppress) w[i] = weight(g);     // (g < c1 <= V: the re-read stays inside the row)
+                ts += w[i];
+            }
+            // exclusive block scan of the thread sums, in id order
+            const float winc = wave_incscan(ts);
+            if (t == 0) { sh_i[0] = 0x7fffffff; sh_i[1] = -1; }
+            if (lane == 63) sh_f[t >> 6] = winc;
+            __syncthreads();
+            float cum = winc - ts;
+            for (int i = 0; i < (t >> 6); ++i) cum += sh_f[i];
+            int first = 0x7fffffff, last = -1;      // first id whose inclusive weight exceeds `rest`; last id of the chunk with any weight (rounding fallback)
+#pragma unroll
+            for (int i = 0; i < ITEMS; ++i) {
+                cum += w[i];
+                if (w[i] > 0.f) {
+                    const int g = sl.g0 + i;
+                    last = g;
+                    if (cum > rest && first == 0x7fffffff) first = g;
+                }
+            }
+            if (first != 0x7fffffff) atomicMin(&sh_i[0], first);
+            if (last >= 0) atomicMax(&sh_i[1], last);
+            __syncthreads();
+            if (t == 0) {
+                const int pick = sh_i[0] != 0x7fffffff ? sh_i[0] : max(sh_i[1], 0);
+                commit_pick<LP, EX, GD>(p, e, gd, row, st, pick, lp, &x[pick], lse);
+            }
+            return;
         }
-        if (first != 0x7fffffff) atomicMin(&sh_i[0], first);
-        if (last >= 0) atomicMax(&sh_i[1], last);
-        __syncthreads();
-        if (t == 0) {
-            const int pick = sh_i[0] != 0x7fffffff ? sh_i[0] : max(sh_i[1], 0);
-            p.out[row] = pick;
-            if (lp) *lp = x[pick] - lse;
-            if constexpr (EX) mark_pick(e, row, pick);
-            if constexpr (GD) guide_advance(gd, row, st, pick);
-        }
-        return;
     }
     const float* cv = p.cand_val + (long long)row * NCHUNK * MAXK;
     const int* ci = p.cand_idx + (long long)row * NCHUNK * MAXK;
@@ -541,15 +498,11 @@ __device__ __forceinline__ void logp_stage2(const SampleArgs& p, const LogpArgs&
         idx[i] = ci[t * NI + i];
         val[i] = cv[t * NI + i];
     }
-    const int K = eff_k(p);
-    const int n = block_topk<NI>(val, idx, K, hist, sh_i, cval, cidx);
+    const int n = block_topk<NI>(val, idx, eff_k(p), hist, sh_i, cval, cidx);
     if (p.temperature <= 0.f) {
         if (t == 0) {
             const int pick = n > 0 ? cidx[0] : 0;
-            p.out[row] = pick;
-            if (lp) *lp = x[pick] - lse;
-            if constexpr (EX) mark_pick(e, row, pick);
-            if constexpr (GD) guide_advance(gd, row, st, pick);
+            commit_pick<LP, EX, GD>(p, e, gd, row, st, pick, lp, &x[pick], lse);
         }
         return;
     }
@@ -560,24 +513,23 @@ __device__ __forceinline__ void logp_stage2(const SampleArgs& p, const LogpArgs&
         for (int j = 0; j < n; ++j) rank += (cval[j] > v) || (cval[j] == v && cidx[j] < id);
         sval[rank] = v;
         sidx[rank] = id;
-        sraw[rank] = x[id];     // every candidate's own logit, fetched by its thread: the serial tail below reads LDS only
+        if constexpr (LP) sraw[rank] = x[id];     // every candidate's own logit, fetched by its thread: the serial tail below reads LDS only
     }
     __syncthreads();
     if (t == 0) {
         const int pick = topk_topp_pick(p, row, sval, cval, n, EX ? e.min_p : 0.f);
-        p.out[row] = sidx[pick];
-        if (lp) *lp = sraw[pick] - lse;
-        if constexpr (EX) mark_pick(e, row, sidx[pick]);
-        if constexpr (GD) guide_advance(gd, row, st, sidx[pick]);
+        commit_pick<LP, EX, GD>(p, e, gd, row, st, sidx[pick], lp, &sraw[pick], lse);
     }
 }
 
-__global__ __launch_bounds__(NT) void sample_logp_stage1(SampleArgs p, LogpArgs q) { logp_stage1<false>(p, q, ExArgs{}); }
-__global__ __launch_bounds__(NT) void sample_logp_stage2(SampleArgs p, LogpArgs q) { logp_stage2<false>(p, q, ExArgs{}); }
-__global__ __launch_bounds__(NT) void sample_ex_stage1(SampleArgs p, LogpArgs q, ExArgs e) { logp_stage1<true>(p, q, e); }
-__global__ __launch_bounds__(NT) void sample_ex_stage2(SampleArgs p, LogpArgs q, ExArgs e) { logp_stage2<true>(p, q, e); }
-__global__ __launch_bounds__(NT) void sample_guided_stage1(SampleArgs p, LogpArgs q, ExArgs e, GuideArgs g) { logp_stage1<true, true>(p, q, e, g); }
-__global__ __launch_bounds__(NT) void sample_guided_stage2(SampleArgs p, LogpArgs q, ExArgs e, GuideArgs g) { logp_stage2<true, true>(p, q, e, g); }
+__global__ __launch_bounds__(NT) void sample_stage1(SampleArgs p) { stage1<false, false, false>(p, LogpArgs{}, ExArgs{}, GuideArgs{}); }
+__global__ __launch_bounds__(NT) void sample_stage2(SampleArgs p) { stage2<false, false, false>(p, LogpArgs{}, ExArgs{}, GuideArgs{}); }
+__global__ __launch_bounds__(NT) void sample_logp_stage1(SampleArgs p, LogpArgs q) { stage1<true, false, false>(p, q, ExArgs{}, GuideArgs{}); }
+__global__ __launch_bounds__(NT) void sample_logp_stage2(SampleArgs p, LogpArgs q) { stage2<true, false, false>(p, q, ExArgs{}, GuideArgs{}); }
+__global__ __launch_bounds__(NT) void sample_ex_stage1(SampleArgs p, LogpArgs q, ExArgs e) { stage1<true, true, false>(p, q, e, GuideArgs{}); }
+__global__ __launch_bounds__(NT) void sample_ex_stage2(SampleArgs p, LogpArgs q, ExArgs e) { stage2<true, true, false>(p, q, e, GuideArgs{}); }
+__global__ __launch_bounds__(NT) void sample_guided_stage1(SampleArgs p, LogpArgs q, ExArgs e, GuideArgs g) { stage1<true, true, true>(p, q, e, g); }
+__global__ __launch_bounds__(NT) void sample_guided_stage2(SampleArgs p, LogpArgs q, ExArgs e, GuideArgs g) { stage2<true, true, true>(p, q, e, g); }
 
 // iadr1_seen_init: one block per sequence zeroes its bitmap row, then ORs in the live tokens of its prompt (left-padded: columns [S - len, S)).
 __global__ __launch_bounds__(NT) void seen_init_kernel(const long long* ids, int S, const int* lengths, int G, int V, unsigned* seen, long long ld_seen) {
@@ -594,115 +546,93 @@ __global__ __launch_bounds__(NT) void seen_init_kernel(const long long* ids, int
     }
 }
 
+enum SamplerPair { PAIR_PLAIN, PAIR_LOGP, PAIR_EX, PAIR_GUIDED };
+
+template <class... A>
+void launch_pair(void (*s1)(A...), void (*s2)(A...), int B, hipStream_t stream, A... a) {
+    hipLaunchKernelGGL(s1, dim3(NCHUNK, B), dim3(NT), 0, stream, a...);
+    hipLaunchKernelGGL(s2, dim3(B), dim3(NT), 0, stream, a...);
+}
+
+// The four entry points: the checks, the workspace carve-up, the argument structs and the launch, once.  `name` is the entry point's ("sample_ex": the prefix of
+// its refusals and the middle of its workspace function's name), `pair` the kernels it launches; under the defaults of what an entry point lacks its checks pass.
+int sample_launch(const char* name, SamplerPair pair, hipStream_t stream, const float* logits, long long ld, long long* out, void* workspace, int B, int V, float temperature,
+                  int top_k, float top_p, int suppress_token, unsigned long long seed, unsigned step, const unsigned* step_ptr, const unsigned long long* seed_ptr,
+                  float* logp_out = nullptr, long long ld_logp = 0, int logp_cols = 0, float min_p = 0.f, float repetition_penalty = 1.f, unsigned* seen = nullptr,
+                  long long ld_seen = 0, int mark_seen = 0, int* state = nullptr, const unsigned* allow = nullptr, long long ld_allow = 0, const short* trans = nullptr,
+                  long long ld_trans = 0, int S = 0) {
+    IADR1_REQUIRE(allow == nullptr || (state != nullptr && trans != nullptr), "%s: allow needs state [B] and trans [S, ld_trans] beside it (got state %s, trans %s)", name,
+                  state ? "a buffer" : "NULL", trans ? "a buffer" : "NULL");
+    IADR1_REQUIRE(allow != nullptr || (state == nullptr && trans == nullptr), "%s: state and trans must be NULL when allow is NULL: without the mask there is no automaton to advance", name);
+    if (allow != nullptr) {
+        IADR1_REQUIRE(S >= 1 && S <= 32767, "%s: S=%d states, outside 1..32767 (trans holds int16)", name, S);
+        IADR1_REQUIRE(ld_allow >= ((long long)V + 31) / 32, "%s: ld_allow=%lld is less than ceil(V / 32) = %lld", name, ld_allow, ((long long)V + 31) / 32);
+        IADR1_REQUIRE(ld_trans >= (long long)V, "%s: ld_trans=%lld is less than V = %d", name, ld_trans, V);
+    }
+    IADR1_REQUIRE(min_p >= 0.f && min_p < 1.f, "%s: min_p must be in [0,1) (got %g)", name, (double)min_p);
+    IADR1_REQUIRE(repetition_penalty > 0.f && repetition_penalty <= 3.402823466e38f, "%s: repetition_penalty must be finite and > 0 (got %g)", name, (double)repetition_penalty);
+    IADR1_REQUIRE((repetition_penalty == 1.f && !mark_seen) || (seen != nullptr && ld_seen >= ((long long)V + 31) / 32),
+                  "%s: repetition_penalty != 1 and mark_seen need a seen bitmap [B, ld_seen] with ld_seen >= ceil(V / 32) (got %s, ld_seen %lld, V %d)", name,
+                  seen ? "a buffer" : "NULL", ld_seen, V);
+    IADR1_REQUIRE(top_p > 0.f && top_p <= 1.f, "%s: top_p must be in (0,1]", name);
+    // (the plain pair has no whole-vocabulary path: top_k <= 0 means MAXK candidates there, under any top_p)
+    IADR1_REQUIRE(pair == PAIR_PLAIN || top_k > 0 || top_p == 1.f, "%s: top_k <= 0 samples the whole vocabulary and takes top_p = 1 only (got %g): a nucleus over all V tokens is not built", name, (double)top_p);
+    IADR1_REQUIRE(B > 0 && V > 0 && workspace != nullptr, "%s: empty problem or missing workspace (iadr1_%s_workspace_bytes)", name, name);
+    IADR1_REQUIRE(V <= NCHUNK * NT * ITEMS, "%s: V=%d exceeds the built maximum %d", name, V, NCHUNK * NT * ITEMS);
+    IADR1_REQUIRE(top_k <= MAXK, "%s: top_k=%d exceeds the built maximum %d", name, top_k, MAXK);
+    IADR1_REQUIRE(logp_out == nullptr || (logp_cols > 0 && ld_logp >= logp_cols), "%s: logp_out needs logp_cols > 0 and ld_logp >= logp_cols", name);
+    float* cv = (float*)workspace;
+    int* ci = (int*)(cv + (long long)B * NCHUNK * MAXK);
+    float* part = (float*)(ci + (long long)B * NCHUNK * MAXK);      // (the plain pair's workspace ends here; it has no LogpArgs)
+    SampleArgs p{logits, ld, out, cv, ci, B, V, temperature, top_p, top_k, suppress_token, (uint32_t)seed, (uint32_t)(seed >> 32), step, step_ptr, seed_ptr};
+    LogpArgs q{part, logp_out, ld_logp, logp_cols};
+    ExArgs e{min_p, repetition_penalty, seen, ld_seen, mark_seen != 0};
+    GuideArgs g{state, allow, trans, ld_allow, ld_trans, S};
+    switch (pair) {
+        case PAIR_PLAIN: launch_pair(sample_stage1, sample_stage2, B, stream, p); break;
+        case PAIR_LOGP: launch_pair(sample_logp_stage1, sample_logp_stage2, B, stream, p, q); break;
+        case PAIR_EX: launch_pair(sample_ex_stage1, sample_ex_stage2, B, stream, p, q, e); break;
+        case PAIR_GUIDED: launch_pair(sample_guided_stage1, sample_guided_stage2, B, stream, p, q, e, g); break;
+    }
+    return iadr1_check_launch(pair == PAIR_PLAIN ? "sample_topk_topp" : name);
+}
+
 }  // namespace
 
 extern "C" long long iadr1_sample_workspace_bytes(int B) { return (long long)B * NCHUNK * MAXK * 8; }
+extern "C" long long iadr1_sample_logp_workspace_bytes(int B) { return (long long)B * NCHUNK * (MAXK * 8 + 16); }
+extern "C" long long iadr1_sample_ex_workspace_bytes(int B) { return iadr1_sample_logp_workspace_bytes(B); }
+extern "C" long long iadr1_sample_guided_workspace_bytes(int B) { return iadr1_sample_ex_workspace_bytes(B); }
 
 extern "C" int iadr1_sample_topk_topp(const float* logits, long long ld, long long* out, void* workspace, int B, int V, float temperature,
                                       int top_k, float top_p, int suppress_token, unsigned long long seed, unsigned step,
                                       const unsigned* step_ptr, const unsigned long long* seed_ptr, hipStream_t stream) {
-    IADR1_REQUIRE(B > 0 && V > 0 && workspace != nullptr, "sample: empty problem or missing workspace (iadr1_sample_workspace_bytes)");
-    IADR1_REQUIRE(V <= NCHUNK * NT * ITEMS, "sample: V=%d exceeds the built maximum %d", V, NCHUNK * NT * ITEMS);
-    IADR1_REQUIRE(top_k <= MAXK, "sample: top_k=%d exceeds the built maximum %d", top_k, MAXK);
-    IADR1_REQUIRE(top_p > 0.f && top_p <= 1.f, "sample: top_p must be in (0,1]");
-    float* cv = (float*)workspace;
-    int* ci = (int*)(cv + (long long)B * NCHUNK * MAXK);
-    SampleArgs p{logits, ld, out, cv, ci, B, V, temperature, top_p, top_k, suppress_token, (uint32_t)seed, (uint32_t)(seed >> 32), step, step_ptr, seed_ptr};
-    hipLaunchKernelGGL(sample_stage1, dim3(NCHUNK, B), dim3(NT), 0, stream, p);
-    hipLaunchKernelGGL(sample_stage2, dim3(B), dim3(NT), 0, stream, p);
-    return iadr1_check_launch("sample_topk_topp");
+    return sample_launch("sample", PAIR_PLAIN, stream, logits, ld, out, workspace, B, V, temperature, top_k, top_p, suppress_token, seed, step, step_ptr, seed_ptr);
 }
-
-extern "C" long long iadr1_sample_logp_workspace_bytes(int B) { return (long long)B * NCHUNK * (MAXK * 8 + 16); }
 
 extern "C" int iadr1_sample_logp(const float* logits, long long ld, long long* out, float* logp_out, long long ld_logp, int logp_cols, void* workspace, int B,
                                  int V, float temperature, int top_k, float top_p, int suppress_token, unsigned long long seed, unsigned step,
                                  const unsigned* step_ptr, const unsigned long long* seed_ptr, hipStream_t stream) {
-    IADR1_REQUIRE(top_p > 0.f && top_p <= 1.f, "sample_logp: top_p must be in (0,1]");
-    IADR1_REQUIRE(top_k > 0 || top_p == 1.f, "sample_logp: top_k <= 0 samples the whole vocabulary and takes top_p = 1 only (got %g): a nucleus over all V tokens is not built", (double)top_p);
-    IADR1_REQUIRE(B > 0 && V > 0 && workspace != nullptr, "sample_logp: empty problem or missing workspace (iadr1_sample_logp_workspace_bytes)");
-    IADR1_REQUIRE(V <= NCHUNK * NT * ITEMS, "sample_logp: V=%d exceeds the built maximum %d", V, NCHUNK * NT * ITEMS);
-    IADR1_REQUIRE(top_k <= MAXK, "sample_logp: top_k=%d exceeds the built maximum %d", top_k, MAXK);
-    IADR1_REQUIRE(logp_out == nullptr || (logp_cols > 0 && ld_logp >= logp_cols), "sample_logp: logp_out needs logp_cols > 0 and ld_logp >= logp_cols");
-    float* cv = (float*)workspace;
-    int* ci = (int*)(cv + (long long)B * NCHUNK * MAXK);
-    float* part = (float*)(ci + (long long)B * NCHUNK * MAXK);
-    SampleArgs p{logits, ld, out, cv, ci, B, V, temperature, top_p, top_k, suppress_token, (uint32_t)seed, (uint32_t)(seed >> 32), step, step_ptr, seed_ptr};
-    LogpArgs q{part, logp_out, ld_logp, logp_cols};
-    hipLaunchKernelGGL(sample_logp_stage1, dim3(NCHUNK, B), dim3(NT), 0, stream, p, q);
-    hipLaunchKernelGGL(sample_logp_stage2, dim3(B), dim3(NT), 0, stream, p, q);
-    return iadr1_check_launch("sample_logp");
+    return sample_launch("sample_logp", PAIR_LOGP, stream, logits, ld, out, workspace, B, V, temperature, top_k, top_p, suppress_token, seed, step, step_ptr, seed_ptr, logp_out,
+                         ld_logp, logp_cols);
 }
-
-extern "C" long long iadr1_sample_ex_workspace_bytes(int B) { return iadr1_sample_logp_workspace_bytes(B); }
 
 extern "C" int iadr1_sample_ex(const float* logits, long long ld, long long* out, float* logp_out, long long ld_logp, int logp_cols, void* workspace, int B,
                                int V, float temperature, int top_k, float top_p, float min_p, float repetition_penalty, unsigned* seen, long long ld_seen,
                                int mark_seen, int suppress_token, unsigned long long seed, unsigned step, const unsigned* step_ptr,
                                const unsigned long long* seed_ptr, hipStream_t stream) {
-    IADR1_REQUIRE(min_p >= 0.f && min_p < 1.f, "sample_ex: min_p must be in [0,1) (got %g)", (double)min_p);
-    IADR1_REQUIRE(repetition_penalty > 0.f && repetition_penalty <= 3.402823466e38f, "sample_ex: repetition_penalty must be finite and > 0 (got %g)", (double)repetition_penalty);
-    IADR1_REQUIRE((repetition_penalty == 1.f && !mark_seen) || (seen != nullptr && ld_seen >= ((long long)V + 31) / 32),
-                  "sample_ex: repetition_penalty != 1 and mark_seen need a seen bitmap [B, ld_seen] with ld_seen >= ceil(V / 32) (got %s, ld_seen %lld, V %d)",
-                  seen ? "a buffer" : "NULL", ld_seen, V);
-    IADR1_REQUIRE(top_p > 0.f && top_p <= 1.f, "sample_ex: top_p must be in (0,1]");
-    IADR1_REQUIRE(top_k > 0 || top_p == 1.f, "sample_ex: top_k <= 0 samples the whole vocabulary and takes top_p = 1 only (got %g): a nucleus over all V tokens is not built", (double)top_p);
-    IADR1_REQUIRE(B > 0 && V > 0 && workspace != nullptr, "sample_ex: empty problem or missing workspace (iadr1_sample_ex_workspace_bytes)");
-    IADR1_REQUIRE(V <= NCHUNK * NT * ITEMS, "sample_ex: V=%d exceeds the built maximum %d", V, NCHUNK * NT * ITEMS);
-    IADR1_REQUIRE(top_k <= MAXK, "sample_ex: top_k=%d exceeds the built maximum %d", top_k, MAXK);
-    IADR1_REQUIRE(logp_out == nullptr || (logp_cols > 0 && ld_logp >= logp_cols), "sample_ex: logp_out needs logp_cols > 0 and ld_logp >= logp_cols");
-    float* cv = (float*)workspace;
-    int* ci = (int*)(cv + (long long)B * NCHUNK * MAXK);
-    float* part = (float*)(ci + (long long)B * NCHUNK * MAXK);
-    SampleArgs p{logits, ld, out, cv, ci, B, V, temperature, top_p, top_k, suppress_token, (uint32_t)seed, (uint32_t)(seed >> 32), step, step_ptr, seed_ptr};
-    LogpArgs q{part, logp_out, ld_logp, logp_cols};
-    ExArgs e{min_p, repetition_penalty, seen, ld_seen, mark_seen != 0};
-    hipLaunchKernelGGL(sample_ex_stage1, dim3(NCHUNK, B), dim3(NT), 0, stream, p, q, e);
-    hipLaunchKernelGGL(sample_ex_stage2, dim3(B), dim3(NT), 0, stream, p, q, e);
-    return iadr1_check_launch("sample_ex");
+    return sample_launch("sample_ex", PAIR_EX, stream, logits, ld, out, workspace, B, V, temperature, top_k, top_p, suppress_token, seed, step, step_ptr, seed_ptr, logp_out,
+                         ld_logp, logp_cols, min_p, repetition_penalty, seen, ld_seen, mark_seen);
 }
-
-extern "C" long long iadr1_sample_guided_workspace_bytes(int B) { return iadr1_sample_ex_workspace_bytes(B); }
 
 extern "C" int iadr1_sample_guided(const float* logits, long long ld, long long* out, float* logp_out, long long ld_logp, int logp_cols, void* workspace, int B,
                                    int V, float temperature, int top_k, float top_p, float min_p, float repetition_penalty, unsigned* seen, long long ld_seen,
                                    int mark_seen, int suppress_token, unsigned long long seed, unsigned step, const unsigned* step_ptr,
                                    const unsigned long long* seed_ptr, int* state, const unsigned* allow, long long ld_allow, const short* trans,
                                    long long ld_trans, int S, hipStream_t stream) {
-    IADR1_REQUIRE(allow == nullptr || (state != nullptr && trans != nullptr), "sample_guided: allow needs state [B] and trans [S, ld_trans] beside it (got state %s, trans %s)",
-                  state ? "a buffer" : "NULL", trans ? "a buffer" : "NULL");
-    IADR1_REQUIRE(allow != nullptr || (state == nullptr && trans == nullptr), "sample_guided: state and trans must be NULL when allow is NULL: without the mask there is no automaton to advance");
-    if (allow != nullptr) {
-        IADR1_REQUIRE(S >= 1 && S <= 32767, "sample_guided: S=%d states, outside 1..32767 (trans holds int16)", S);
-        IADR1_REQUIRE(ld_allow >= ((long long)V + 31) / 32, "sample_guided: ld_allow=%lld is less than ceil(V / 32) = %lld", ld_allow, ((long long)V + 31) / 32);
-        IADR1_REQUIRE(ld_trans >= (long long)V, "sample_guided: ld_trans=%lld is less than V = %d", ld_trans, V);
-    }
-    IADR1_REQUIRE(min_p >= 0.f && min_p < 1.f, "sample_guided: min_p must be in [0,1) (got %g)", (double)min_p);
-    IADR1_REQUIRE(repetition_penalty > 0.f && repetition_penalty <= 3.402823466e38f, "sample_guided: repetition_penalty must be finite and > 0 (got %g)", (double)repetition_penalty);
-    IADR1_REQUIRE((repetition_penalty == 1.f && !mark_seen) || (seen != nullptr && ld_seen >= ((long long)V + 31) / 32),
-                  "sample_guided: repetition_penalty != 1 and mark_seen need a seen bitmap [B, ld_seen] with ld_seen >= ceil(V / 32) (got %s, ld_seen %lld, V %d)",
-                  seen ? "a buffer" : "NULL", ld_seen, V);
-    IADR1_REQUIRE(top_p > 0.f && top_p <= 1.f, "sample_guided: top_p must be in (0,1]");
-    IADR1_REQUIRE(top_k > 0 || top_p == 1.f, "sample_guided: top_k <= 0 samples the whole vocabulary and takes top_p = 1 only (got %g): a nucleus over all V tokens is not built", (double)top_p);
-    IADR1_REQUIRE(B > 0 && V > 0 && workspace != nullptr, "sample_guided: empty problem or missing workspace (iadr1_sample_guided_workspace_bytes)");
-    IADR1_REQUIRE(V <= NCHUNK * NT * ITEMS, "sample_guided: V=%d exceeds the built maximum %d", V, NCHUNK * NT * ITEMS);
-    IADR1_REQUIRE(top_k <= MAXK, "sample_guided: top_k=%d exceeds the built maximum %d", top_k, MAXK);
-    IADR1_REQUIRE(logp_out == nullptr || (logp_cols > 0 && ld_logp >= logp_cols), "sample_guided: logp_out needs logp_cols > 0 and ld_logp >= logp_cols");
-    float* cv = (float*)workspace;
-    int* ci = (int*)(cv + (long long)B * NCHUNK * MAXK);
-    float* part = (float*)(ci + (long long)B * NCHUNK * MAXK);
-    SampleArgs p{logits, ld, out, cv, ci, B, V, temperature, top_p, top_k, suppress_token, (uint32_t)seed, (uint32_t)(seed >> 32), step, step_ptr, seed_ptr};
-    LogpArgs q{part, logp_out, ld_logp, logp_cols};
-    ExArgs e{min_p, repetition_penalty, seen, ld_seen, mark_seen != 0};
-    if (allow == nullptr) {     // no guide: iadr1_sample_ex's own kernels, the same device code and the same bits
-        hipLaunchKernelGGL(sample_ex_stage1, dim3(NCHUNK, B), dim3(NT), 0, stream, p, q, e);
-        hipLaunchKernelGGL(sample_ex_stage2, dim3(B), dim3(NT), 0, stream, p, q, e);
-        return iadr1_check_launch("sample_guided");
-    }
-    GuideArgs g{state, allow, trans, ld_allow, ld_trans, S};
-    hipLaunchKernelGGL(sample_guided_stage1, dim3(NCHUNK, B), dim3(NT), 0, stream, p, q, e, g);
-    hipLaunchKernelGGL(sample_guided_stage2, dim3(B), dim3(NT), 0, stream, p, q, e, g);
-    return iadr1_check_launch("sample_guided");
+    // no guide: iadr1_sample_ex's own kernels, the same device code and the same bits
+    return sample_launch("sample_guided", allow != nullptr ? PAIR_GUIDED : PAIR_EX, stream, logits, ld, out, workspace, B, V, temperature, top_k, top_p, suppress_token, seed, step,
+                         step_ptr, seed_ptr, logp_out, ld_logp, logp_cols, min_p, repetition_penalty, seen, ld_seen, mark_seen, state, allow, ld_allow, trans, ld_trans, S);
 }
 
 extern "C" int iadr1_seen_init(const long long* ids, int S, const int* lengths, int Bp, int G, int V, unsigned* seen, long long ld_seen, hipStream_t stream) {

@@ -661,44 +661,44 @@ def grpo_loss_ex(logp, adv, mask, beta, *, ref_logp=None, old_logp=None, rollout
     return dlogp, kl, row_loss, row_kl
 
 
-_sample_ws = {}
+_sample_ws = {}     # (B, device) -> the workspace of all four samplers: iadr1_sample_logp_workspace_bytes is the largest of their sizes
+
+
+def _sample(name, logits32, temperature, top_k, top_p, seed, step, suppress_token, step_ptr, out, seed_ptr, logp_out=None, want_logp=False, ex=None, guide=None):
+    """The work of the four wrappers below.  name: the wrapper's, and from sample_logp onwards (the calls that take logp_out) the library call's; ex: (min_p,
+    repetition_penalty, seen, mark_seen) from sample_ex onwards; guide: (state, allow, trans) for sample_guided.  Returns (ids, logp_out or None)."""
+    B, V = logits32.shape
+    key = (B, logits32.device)
+    o = out if out is not None else torch.empty(B, dtype=torch.int64, device=logits32.device)
+    if logp_out is None and want_logp:
+        assert step_ptr is None and int(step) == 0, f"{name}: give logp_out [B, cols] when the step (the column) is not 0"
+        logp_out = torch.zeros(B, 1, dtype=F32, device=logits32.device)
+    if key not in _sample_ws:
+        _sample_ws[key] = torch.empty(hip.lib().iadr1_sample_logp_workspace_bytes(B), dtype=torch.uint8, device=logits32.device)
+    logp_args = () if name == "sample" else (logp_out, _ld(logp_out) if logp_out is not None else 0, logp_out.shape[1] if logp_out is not None else 0)
+    min_p, repetition_penalty, seen, mark_seen = ex or (0.0, 1.0, None, False)
+    assert seen is None or (seen.dim() == 2 and seen.shape[0] == B and seen.element_size() == 4 and seen.stride(1) == 1), f"{name}: seen is [B, words] of 32-bit words"
+    ex_args = () if ex is None else (float(min_p), float(repetition_penalty), seen, seen.stride(0) if seen is not None else 0, int(bool(mark_seen)))
+    state, allow, trans = guide or (None, None, None)
+    S = allow.shape[0] if allow is not None else 0
+    assert allow is None or (allow.dim() == 2 and allow.element_size() == 4 and allow.stride(1) == 1), f"{name}: allow is [S, words] of 32-bit words"
+    assert allow is None or (trans is not None and trans.dim() == 2 and trans.dtype == torch.int16 and trans.stride(1) == 1 and trans.shape[0] == S), f"{name}: trans is [S, >= V] int16"
+    assert allow is None or (state is not None and state.dtype == torch.int32 and state.dim() == 1 and state.numel() == B and state.stride(0) == 1), f"{name}: state is [B] int32"
+    guide_args = () if guide is None else (state, allow, allow.stride(0) if allow is not None else 0, trans, trans.stride(0) if trans is not None else 0, S)
+    hip.call("sample_topk_topp" if name == "sample" else name, logits32, _ld(logits32), o, *logp_args, _sample_ws[key], B, V, float(temperature), int(top_k), float(top_p), *ex_args,
+             int(suppress_token), int(seed), int(step), step_ptr, seed_ptr, *guide_args)
+    return o, logp_out
 
 
 def sample(logits32, temperature, top_k, top_p, seed, step, suppress_token=-1, step_ptr=None, out=None, seed_ptr=None):
-    B, V = logits32.shape
-    o = out if out is not None else torch.empty(B, dtype=torch.int64, device=logits32.device)
-    key = (B, logits32.device)
-    ws = _sample_ws.get(key)
-    if ws is None:
-        ws = torch.empty(hip.lib().iadr1_sample_workspace_bytes(B), dtype=torch.uint8, device=logits32.device)
-        _sample_ws[key] = ws
-    hip.call("sample_topk_topp", logits32, _ld(logits32), o, ws, B, V, float(temperature), int(top_k), float(top_p), int(suppress_token), int(seed), int(step), step_ptr, seed_ptr)
-    return o
-
-
-_sample_logp_ws = {}
+    return _sample("sample", logits32, temperature, top_k, top_p, seed, step, suppress_token, step_ptr, out, seed_ptr)[0]
 
 
 def sample_logp(logits32, temperature, top_k, top_p, seed, step, suppress_token=-1, step_ptr=None, out=None, seed_ptr=None, logp_out=None, want_logp=True):
     """iadr1_sample_logp: `sample` (bit-equal ids for top_k in 1..64) + whole-vocabulary sampling for top_k <= 0 (top_p must be 1) + the temperature-1,
     unfiltered log-prob of every pick.  logp_out: [B, cols] fp32, written at column step (*step_ptr when given), untouched when that is >= cols; None with
     want_logp: a fresh [B, 1] tensor is used (step must then be 0 and step_ptr None).  Returns (ids, logp_out or None)."""
-    B, V = logits32.shape
-    o = out if out is not None else torch.empty(B, dtype=torch.int64, device=logits32.device)
-    if logp_out is None and want_logp:
-        assert step_ptr is None and int(step) == 0, "sample_logp: give logp_out [B, cols] when the step (the column) is not 0"
-        logp_out = torch.zeros(B, 1, dtype=F32, device=logits32.device)
-    key = (B, logits32.device)
-    ws = _sample_logp_ws.get(key)
-    if ws is None:
-        ws = torch.empty(hip.lib().iadr1_sample_logp_workspace_bytes(B), dtype=torch.uint8, device=logits32.device)
-        _sample_logp_ws[key] = ws
-    hip.call("sample_logp", logits32, _ld(logits32), o, logp_out, _ld(logp_out) if logp_out is not None else 0, logp_out.shape[1] if logp_out is not None else 0, ws, B, V,
-             float(temperature), int(top_k), float(top_p), int(suppress_token), int(seed), int(step), step_ptr, seed_ptr)
-    return o, logp_out
-
-
-_sample_ex_ws = {}
+    return _sample("sample_logp", logits32, temperature, top_k, top_p, seed, step, suppress_token, step_ptr, out, seed_ptr, logp_out, want_logp)
 
 
 def sample_ex(logits32, temperature, top_k, top_p, seed, step, min_p=0.0, repetition_penalty=1.0, seen=None, mark_seen=False, suppress_token=-1, step_ptr=None, out=None,
@@ -706,22 +706,7 @@ def sample_ex(logits32, temperature, top_k, top_p, seed, step, min_p=0.0, repeti
     """iadr1_sample_ex: `sample_logp` with a repetition penalty over the per-sequence bitmap `seen` ([B, >= ceil(V / 32)] 32-bit words: int32 or uint32) in front
     of the filter and a min_p cut behind it; mark_seen: the pick's bit is set in seen[row] inside the call.  logp_out keeps sample_logp's meaning (raw logits,
     temperature 1, no penalty, no filter).  With min_p 0, repetition_penalty 1 and mark_seen False the result is bit-equal to sample_logp's.  Returns (ids, logp_out or None)."""
-    B, V = logits32.shape
-    o = out if out is not None else torch.empty(B, dtype=torch.int64, device=logits32.device)
-    if logp_out is None and want_logp:
-        assert step_ptr is None and int(step) == 0, "sample_ex: give logp_out [B, cols] when the step (the column) is not 0"
-        logp_out = torch.zeros(B, 1, dtype=F32, device=logits32.device)
-    if seen is not None:
-        assert seen.dim() == 2 and seen.shape[0] == B and seen.element_size() == 4 and seen.stride(1) == 1, "sample_ex: seen is [B, words] of 32-bit words"
-    key = (B, logits32.device)
-    ws = _sample_ex_ws.get(key)
-    if ws is None:
-        ws = torch.empty(hip.lib().iadr1_sample_ex_workspace_bytes(B), dtype=torch.uint8, device=logits32.device)
-        _sample_ex_ws[key] = ws
-    hip.call("sample_ex", logits32, _ld(logits32), o, logp_out, _ld(logp_out) if logp_out is not None else 0, logp_out.shape[1] if logp_out is not None else 0, ws, B, V,
-             float(temperature), int(top_k), float(top_p), float(min_p), float(repetition_penalty), seen, seen.stride(0) if seen is not None else 0, int(bool(mark_seen)),
-             int(suppress_token), int(seed), int(step), step_ptr, seed_ptr)
-    return o, logp_out
+    return _sample("sample_ex", logits32, temperature, top_k, top_p, seed, step, suppress_token, step_ptr, out, seed_ptr, logp_out, want_logp, ex=(min_p, repetition_penalty, seen, mark_seen))
 
 
 def sample_guided(logits32, temperature, top_k, top_p, seed, step, state=None, allow=None, trans=None, min_p=0.0, repetition_penalty=1.0, seen=None, mark_seen=False,
@@ -729,29 +714,8 @@ def sample_guided(logits32, temperature, top_k, top_p, seed, step, state=None, a
     """iadr1_sample_guided: `sample_ex` behind an automaton's allowed-token mask.  state [B] int32 (read and written), allow [S, >= ceil(V / 32)] 32-bit words,
     trans [S, >= V] int16; tokens whose bit is clear in allow[state[row]] are -inf to the filter, and state[row] <- trans[state[row], pick] after the pick.
     logp_out keeps sample_logp's meaning (raw logits, no mask).  All three None: bit-equal to sample_ex.  Returns (ids, logp_out or None)."""
-    B, V = logits32.shape
-    o = out if out is not None else torch.empty(B, dtype=torch.int64, device=logits32.device)
-    if logp_out is None and want_logp:
-        assert step_ptr is None and int(step) == 0, "sample_guided: give logp_out [B, cols] when the step (the column) is not 0"
-        logp_out = torch.zeros(B, 1, dtype=F32, device=logits32.device)
-    if seen is not None:
-        assert seen.dim() == 2 and seen.shape[0] == B and seen.element_size() == 4 and seen.stride(1) == 1, "sample_guided: seen is [B, words] of 32-bit words"
-    S = 0
-    if allow is not None:
-        S = allow.shape[0]
-        assert allow.dim() == 2 and allow.element_size() == 4 and allow.stride(1) == 1, "sample_guided: allow is [S, words] of 32-bit words"
-        assert trans is not None and trans.dim() == 2 and trans.dtype == torch.int16 and trans.stride(1) == 1 and trans.shape[0] == S, "sample_guided: trans is [S, >= V] int16"
-        assert state is not None and state.dtype == torch.int32 and state.dim() == 1 and state.numel() == B and state.stride(0) == 1, "sample_guided: state is [B] int32"
-    key = (B, logits32.device)
-    ws = _sample_ex_ws.get(key)     # (iadr1_sample_guided_workspace_bytes == iadr1_sample_ex_workspace_bytes: one buffer serves both)
-    if ws is None:
-        ws = torch.empty(hip.lib().iadr1_sample_guided_workspace_bytes(B), dtype=torch.uint8, device=logits32.device)
-        _sample_ex_ws[key] = ws
-    hip.call("sample_guided", logits32, _ld(logits32), o, logp_out, _ld(logp_out) if logp_out is not None else 0, logp_out.shape[1] if logp_out is not None else 0, ws, B, V,
-             float(temperature), int(top_k), float(top_p), float(min_p), float(repetition_penalty), seen, seen.stride(0) if seen is not None else 0, int(bool(mark_seen)),
-             int(suppress_token), int(seed), int(step), step_ptr, seed_ptr, state, allow, allow.stride(0) if allow is not None else 0, trans,
-             trans.stride(0) if trans is not None else 0, int(S))
-    return o, logp_out
+    return _sample("sample_guided", logits32, temperature, top_k, top_p, seed, step, suppress_token, step_ptr, out, seed_ptr, logp_out, want_logp,
+                   ex=(min_p, repetition_penalty, seen, mark_seen), guide=(state, allow, trans))
 
 
 def seen_init(ids, lengths, G, V, seen):

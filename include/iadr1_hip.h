@@ -347,6 +347,10 @@ int iadr1_sample_topk_topp(const float* logits, long long ld, long long* out, vo
                            const unsigned* step_ptr, const unsigned long long* seed_ptr, iadr1_stream_t stream);
 /* step_ptr / seed_ptr: optional device-resident step counter / seed that replace the scalar arguments (a captured hipGraph freezes
  * kernel arguments: the rollout replays one graph for every decode step of every optimizer step). */
+/* The four entry points of this section are one device body per stage behind four kernel pairs (csrc/sample.hip: stage1 / stage2 <LP, EX, GD>, each entry point launches
+ * its own instantiations) and one host function: two of them give the same bits wherever what the newer one adds is neutral, and every refusal carries its entry point's
+ * prefix ("sample:", "sample_logp:", "sample_ex:", "sample_guided:").  top_k <= 0 means 64 candidates in iadr1_sample_topk_topp and the whole vocabulary from
+ * iadr1_sample_logp onwards. */
 /* iadr1_sample_logp: the same sampler, plus what vLLM returns beside the token ids and what its evaluation callers sample with.
  *   top_k in 1..64: filter semantics, Philox stream and token ids of iadr1_sample_topk_topp, bit for bit (greedy, suppress_token, step_ptr, seed_ptr included).
  *   top_k <= 0: the WHOLE vocabulary -- vLLM SamplingParams(temperature=T, top_p=1.0) of the LLaVA evaluation script

@@ -146,6 +146,56 @@ def test_whole_vocabulary_frequencies():
     assert chi2 < (n - 1) + 4.5 * math.sqrt(2 * (n - 1)) + 4, f"chi2 {chi2:.1f} for {n - 1} dof"
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("V", [33, 8200, 20011])
+def test_slice_geometries_between_the_tested_vocabularies(V):
+    """(4b) The slice geometries VOCABS does not reach (csize = ceil(V / 32) ids per chunk, per = ceil(csize / 256) ids per thread): V = 33: csize 2, per 1, chunks
+    17..31 empty and top_k = 50 clamped to 33; V = 8200: csize 257, per 2, last chunk 233 of 257; V = 20011: csize 626, per 3, last chunk 605 of 626.  20 steps each.
+    (a) greedy: sample, sample_logp and neutral sample_ex give argmax.  (b) T 0.9, top-k 50, top-p 0.9: the four entry points give the same ids, every id is in the
+    oracle's candidate set and equals the oracle's pick wherever its margin exceeds 1e-4 (test_sampler_greedy_and_topk_topp's rule); at most 4 of the 320 draws may
+    be skipped that way (the oracle alone skips 2 of 320 at each V).  (c) whole vocabulary, with and without a suppressed token: every draw inside the inverse-CDF
+    bracket of (3) at tol = 1e-4 * cdf[-1], none skipped, and logp_out against float64 log_softmax at (1e-5, 1e-5)."""
+    from oracle import sampler as osamp
+    B, T, seed, STEPS = 16, 0.9, 1234567890123, 20
+    lg = rnd(B, V, seed=1, scale=2.5)
+    lgc = lg.cpu().numpy()
+    x = lgc.astype(np.float64)
+    sup = int(lg[5].argmax())
+    amax = lg.argmax(-1)
+    assert torch.equal(ops.sample(lg, 0.0, 50, 0.9, seed=seed, step=0), amax)
+    assert torch.equal(ops.sample_logp(lg, 0.0, 50, 0.9, seed=seed, step=0, want_logp=False)[0], amax)
+    assert torch.equal(ops.sample_ex(lg, 0.0, 50, 0.9, seed=seed, step=0, want_logp=False)[0], amax)
+    cand = [set(osamp.candidates(lgc[b], T, 50, 0.9)[0].tolist()) for b in range(B)]
+    skipped = 0
+    for step in range(STEPS):
+        got = ops.sample(lg, T, 50, 0.9, seed=seed, step=step)
+        assert torch.equal(got, ops.sample_logp(lg, T, 50, 0.9, seed=seed, step=step, want_logp=False)[0]), step
+        assert torch.equal(got, ops.sample_ex(lg, T, 50, 0.9, seed=seed, step=step, want_logp=False)[0]), step
+        assert torch.equal(got, ops.sample_guided(lg, T, 50, 0.9, seed=seed, step=step, want_logp=False)[0]), step
+        for b, t in enumerate(got.tolist()):
+            assert t in cand[b], "sampled token outside the top-k/top-p candidate set"
+            ref, margin = osamp.sample_row(lgc[b], T, 50, 0.9, seed, b, step)
+            if margin > 1e-4:
+                assert t == ref, (V, step, b, t, ref, margin)
+            else:
+                skipped += 1
+    print(f"[slice geometries] V={V}: {skipped} of {B * STEPS} top-k/top-p draws within 1e-4 of a CDF edge")
+    assert skipped <= 4
+    for s in (-1, sup):
+        cdfs = [_cdf(x[b], T, s) for b in range(B)]
+        lp = torch.zeros(B, STEPS, device=DEV)
+        for step in range(STEPS):
+            got = ops.sample_logp(lg, T, 0, 1.0, seed=seed, step=step, suppress_token=s, logp_out=lp)[0]
+            close(lp[:, step], ref_logp(lg, got), 1e-5, 1e-5, f"logp V={V} suppress={s} step={step}")
+            for b, t in enumerate(got.tolist()):
+                cdf = cdfs[b]
+                tol = 1e-4 * cdf[-1]
+                u = osamp.philox_uniform(seed, b, step) * cdf[-1]
+                assert 0 <= t < V and t != s
+                lo = cdf[t - 1] if t > 0 else 0.0
+                assert lo - tol <= u <= cdf[t] + tol, (V, s, step, b, t, lo / cdf[-1], u / cdf[-1], cdf[t] / cdf[-1])
+
+
 def test_a_nucleus_over_the_whole_vocabulary_is_refused_without_a_gpu():
     """(5) top_p < 1 with top_k <= 0: rc < 0 and a message through iadr1_last_error, detected on the host."""
     L = hip.lib()

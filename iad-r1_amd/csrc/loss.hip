@@ -9,6 +9,7 @@
 // grpo_loss: sc_grpo_trainer.py:746,796-798,816 for one rank's [N,C] completion block.  grpo_loss_is: the same with a truncated importance weight per token.
 // grpo_loss_clip: the clipped surrogate of trl's GRPOTrainer (trl/trl/trainer/grpo_trainer.py:1203-1213) for optimizer steps that reuse a rollout (num_iterations > 1).
 // grpo_loss_ex: the same three kernels behind one entry point, with the row normaliser of trl's loss_type (grpo_trainer.py:1212-1219) and an optional reference.
+// grpo_loss_sel: grpo_loss_ex with a per-token 0/1 selector on the advantage term (trl's top_entropy_quantile mask, grpo_trainer.py get_high_entropy_mask).
 #include "common.h"
 
 namespace {
@@ -75,13 +76,22 @@ __device__ __forceinline__ float ref_gap(const float* ref_logp, const float* log
 // The three loss kernels share two parameters.  REF: see ref_gap.  row_scale: 0 = every row's sums are divided by its live-token count (inv = 1 / cnt, trl's
 // loss_type "grpo"); > 0 = this factor instead, the same for every row ("bnpo": rows / live tokens of the batch, "dr_grpo": 1 / max_completion_length).  It
 // replaces inv in row_loss and dlogp only: row_kl and the sequence-level importance ratio stay means over cnt.
+// SEL (iadr1_grpo_loss_sel): sel [N, C] of 0 / 1 in the layout of mask gates the ADVANTAGE part of a token's term and of its gradient -- with q = sel_i the term
+// is w (-(q s - beta kl)), s = A or min(r A, rc A).  The KL part, kl_out, row_kl, cnt, the importance ratio, row_stats and the clip counts keep running over the
+// live tokens.  The gate is a select in front of the expression (never a product by 1.0f), so that with q = 1 every expression is the SEL = false one on the
+// same operands.  SEL false: no load through sel exists.
+template <bool SEL>
+__device__ __forceinline__ float gated(const int* sel, int i, float a) {
+    if constexpr (SEL) return sel[i] != 0 ? a : 0.f;
+    else return a;
+}
 
 // One block per sequence row.  Outputs: dlogp [N,C] (gradient of the batch loss w.r.t. the policy
 // log-probs), per-token kl [N,C], and per-row partials row_loss[N], row_kl[N] (means over the mask).
-template <bool REF>
+template <bool REF, bool SEL = false>
 __global__ __launch_bounds__(256) void grpo_loss_kernel(const float* logp, const float* ref_logp, const float* adv, const int* mask,
                                                         float beta, float inv_nrows, float row_scale, float* dlogp, float* kl_out, float* row_loss,
-                                                        float* row_kl, int N, int C) {
+                                                        float* row_kl, int N, int C, const int* sel = nullptr) {
     __shared__ float scratch[16];
     const int n = blockIdx.x;
     const float A = adv[n];
@@ -94,7 +104,8 @@ __global__ __launch_bounds__(256) void grpo_loss_kernel(const float* logp, const
         const float m = (float)mask[i];
         if (kl_out) kl_out[i] = kl;
         cnt += m;
-        sl += m * (-(A - beta * kl));  // exp(p - p.detach()) == 1 in value
+        const float Aq = gated<SEL>(sel, i, A);
+        sl += m * (-(Aq - beta * kl));  // exp(p - p.detach()) == 1 in value
         sk += m * kl;
     }
     cnt = block_sum<256>(cnt, scratch);
@@ -110,7 +121,8 @@ __global__ __launch_bounds__(256) void grpo_loss_kernel(const float* logp, const
         const int i = n * C + c;
         const float d = ref_gap<REF>(ref_logp, logp, i);
         // d/dp [ -(exp(p - sg p) A - beta (exp(r-p) - (r-p) - 1)) ] = -A + beta (1 - exp(r-p))
-        dlogp[i] = (float)mask[i] * scale * inv_nrows * (-A + beta * (1.f - __expf(d)));
+        const float Aq = gated<SEL>(sel, i, A);
+        dlogp[i] = (float)mask[i] * scale * inv_nrows * (-Aq + beta * (1.f - __expf(d)));
     }
 }
 
@@ -120,10 +132,11 @@ __global__ __launch_bounds__(256) void grpo_loss_kernel(const float* logp, const
 // (rollout_logp == 0 there by the rollout's contract) get d = 0 by a select and never reach an exp that feeds a sum.  With w == 1 every expression below rounds
 // as grpo_loss_kernel's does (1 * x is exact), so the four shared outputs are then bit-equal to that kernel's.
 // row_stats[n][5] = { sum m w, live tokens whose untruncated ratio exceeded cap, sum m |d|, max m |d|, sum m (exp(d) - d - 1) }.
-template <bool REF>
+template <bool REF, bool SEL = false>
 __global__ __launch_bounds__(256) void grpo_loss_is_kernel(const float* logp, const float* ref_logp, const float* rollout_logp, const float* adv,
                                                            const int* mask, float beta, float cap, int level, float inv_nrows, float row_scale, float* dlogp,
-                                                           float* kl_out, float* row_loss, float* row_kl, float* w_out, float* row_stats, int N, int C) {
+                                                           float* kl_out, float* row_loss, float* row_kl, float* w_out, float* row_stats, int N, int C,
+                                                           const int* sel = nullptr) {
     __shared__ float scratch[16];
     const int n = blockIdx.x;
     const float A = adv[n];
@@ -152,7 +165,8 @@ __global__ __launch_bounds__(256) void grpo_loss_is_kernel(const float* logp, co
         const float dq = live ? logp[i] - rollout_logp[i] : 0.f;
         const float ratio = __expf(dq);
         const float w = level == 0 ? (ratio > cap ? cap : ratio) : w_row;
-        const float t = -(A - beta * kl);
+        const float Aq = gated<SEL>(sel, i, A);
+        const float t = -(Aq - beta * kl);
         sl += m * (w * t);
         sk += m * kl;
         if (live) {
@@ -183,7 +197,8 @@ __global__ __launch_bounds__(256) void grpo_loss_is_kernel(const float* logp, co
         const float ratio = __expf(live ? logp[i] - rollout_logp[i] : 0.f);
         const float w = level == 0 ? (ratio > cap ? cap : ratio) : w_row;
         // grpo_loss_kernel's expression, then the weight: the product by w stays outside so that nothing of the unweighted value is contracted differently
-        const float g = (float)mask[i] * scale * inv_nrows * (-A + beta * (1.f - __expf(d)));
+        const float Aq = gated<SEL>(sel, i, A);
+        const float g = (float)mask[i] * scale * inv_nrows * (-Aq + beta * (1.f - __expf(d)));
         dlogp[i] = w * g;
         if (w_out) w_out[i] = live ? w : 0.f;
     }
@@ -197,10 +212,10 @@ __global__ __launch_bounds__(256) void grpo_loss_is_kernel(const float* logp, co
 // and s = A exactly, so every expression below rounds as grpo_loss_is_kernel's (and, with w == 1, grpo_loss_kernel's) does: the products r * A sit behind a
 // min / a select, where nothing contracts them into the sums that follow.
 // row_stats[n][4] = { low-clipped live tokens, high-clipped live tokens, sum m r, max m |d| }.
-template <bool REF>
+template <bool REF, bool SEL = false>
 __global__ __launch_bounds__(256) void grpo_loss_clip_kernel(const float* logp, const float* old_logp, const float* ref_logp, const float* adv, const int* mask,
                                                              const float* w_in, float beta, float lo, float hi, float inv_nrows, float row_scale, float* dlogp, float* kl_out,
-                                                             float* row_loss, float* row_kl, float* row_stats, int N, int C) {
+                                                             float* row_loss, float* row_kl, float* row_stats, int N, int C, const int* sel = nullptr) {
     __shared__ float scratch[16];
     const int n = blockIdx.x;
     const float A = adv[n];
@@ -216,7 +231,7 @@ __global__ __launch_bounds__(256) void grpo_loss_clip_kernel(const float* logp, 
         const float dq = live ? logp[i] - old_logp[i] : 0.f;
         const float r = __expf(dq);
         const float rc = fminf(fmaxf(r, lo), hi);
-        const float s = fminf(r * A, rc * A);
+        const float s = gated<SEL>(sel, i, fminf(r * A, rc * A));
         const float w = w_in ? w_in[i] : 1.f;
         const float t = -(s - beta * kl);
         cnt += m;
@@ -251,7 +266,7 @@ __global__ __launch_bounds__(256) void grpo_loss_clip_kernel(const float* logp, 
         const float r = __expf(live ? logp[i] - old_logp[i] : 0.f);
         const bool clipped = (r < lo && A < 0.f) || (r > hi && A > 0.f);
         // d/dp min(r A, rc A) = r A where the unclamped branch is the min, 0 where the clamped one is
-        const float ga = clipped ? 0.f : r * A;
+        const float ga = gated<SEL>(sel, i, clipped ? 0.f : r * A);
         const float w = w_in ? w_in[i] : 1.f;
         // grpo_loss_kernel's expression with r A for A, then the weight (as in grpo_loss_is_kernel).  Both of those compile -A + beta (1 - e) to a rounded product
         // and a subtraction (the two products of the line pair up into packed multiplies, which leaves nothing to contract); the select in front of ga would let
@@ -316,41 +331,58 @@ extern "C" int iadr1_grpo_loss_clip(const float* logp, const float* old_logp, co
 }
 // The three forms above behind one entry point: which one runs follows from which of old_logp / rollout_logp is given, REF from ref_logp, and row_scale is
 // handed through.  With ref_logp given and row_scale == 0 the launch is the old entry point's, argument for argument.
+// SEL: iadr1_grpo_loss_sel's selector; `name` is the entry point's, the prefix of its refusals.
+namespace {
+template <bool SEL>
+int grpo_loss_ex_launch(const char* name, const float* logp, const float* ref_logp, const float* old_logp, const float* rollout_logp, const float* w, const float* adv,
+                        const int* mask, float beta, float cap, int level, float eps_low, float eps_high, float row_scale, int n_total_rows, float* dlogp, float* kl,
+                        float* row_loss, float* row_kl, float* w_out, float* row_stats, int N, int C, const int* sel, hipStream_t stream) {
+    IADR1_REQUIRE(N > 0, "%s: N must be > 0 (got %d)", name, N);
+    IADR1_REQUIRE(C > 0, "%s: C must be > 0 (got %d)", name, C);
+    IADR1_REQUIRE(n_total_rows >= N, "%s: n_total_rows (%d) is smaller than N (%d): it is the row count of the whole step", name, n_total_rows, N);
+    IADR1_REQUIRE(ref_logp != nullptr || beta == 0.f, "%s: ref_logp is null with beta = %g: the KL term needs the reference's log-probs (only beta == 0 runs without them)", name, (double)beta);
+    IADR1_REQUIRE(row_scale >= 0.f && row_scale <= 3.402823466e38f /* false for NaN and +inf */, "%s: row_scale must be 0 (1 / live tokens of the row) or finite and > 0 (got %g)", name, (double)row_scale);
+    IADR1_REQUIRE(old_logp == nullptr || rollout_logp == nullptr, "%s: old_logp and rollout_logp are both given: a reuse step takes the cached weights as w, not the rollout's log-probs", name);
+    IADR1_REQUIRE(w == nullptr || old_logp != nullptr, "%s: w is given without old_logp (the weights belong to the clipped form)", name);
+    IADR1_REQUIRE(row_stats != nullptr || (old_logp == nullptr && rollout_logp == nullptr), "%s: row_stats is null (the %s form writes [N, %d] partials)", name, old_logp ? "clip" : "IS", old_logp ? 4 : 5);
+    const float inv_nrows = 1.f / (float)n_total_rows;
+    if (old_logp != nullptr) {
+        IADR1_REQUIRE(eps_low >= 0.f && eps_low < 1.f /* false for NaN */, "%s: eps_low must be in [0, 1) (got %g)", name, (double)eps_low);
+        IADR1_REQUIRE(eps_high >= 0.f && eps_high <= 3.402823466e38f /* false for NaN and +inf */, "%s: eps_high must be finite and >= 0 (got %g)", name, (double)eps_high);
+        if (ref_logp != nullptr)
+            hipLaunchKernelGGL((grpo_loss_clip_kernel<true, SEL>), dim3(N), dim3(256), 0, stream, logp, old_logp, ref_logp, adv, mask, w, beta, 1.f - eps_low, 1.f + eps_high,
+                               inv_nrows, row_scale, dlogp, kl, row_loss, row_kl, row_stats, N, C, sel);
+        else
+            hipLaunchKernelGGL((grpo_loss_clip_kernel<false, SEL>), dim3(N), dim3(256), 0, stream, logp, old_logp, ref_logp, adv, mask, w, beta, 1.f - eps_low, 1.f + eps_high,
+                               inv_nrows, row_scale, dlogp, kl, row_loss, row_kl, row_stats, N, C, sel);
+    } else if (rollout_logp != nullptr) {
+        IADR1_REQUIRE(cap >= 1.f && cap <= 3.402823466e38f /* false for NaN and +inf */, "%s: cap must be finite and >= 1 (got %g): a smaller cap would down-weight on-policy tokens", name, (double)cap);
+        IADR1_REQUIRE(level == 0 || level == 1, "%s: unknown level %d (0 = token, 1 = sequence)", name, level);
+        if (ref_logp != nullptr)
+            hipLaunchKernelGGL((grpo_loss_is_kernel<true, SEL>), dim3(N), dim3(256), 0, stream, logp, ref_logp, rollout_logp, adv, mask, beta, cap, level, inv_nrows, row_scale,
+                               dlogp, kl, row_loss, row_kl, w_out, row_stats, N, C, sel);
+        else
+            hipLaunchKernelGGL((grpo_loss_is_kernel<false, SEL>), dim3(N), dim3(256), 0, stream, logp, ref_logp, rollout_logp, adv, mask, beta, cap, level, inv_nrows, row_scale,
+                               dlogp, kl, row_loss, row_kl, w_out, row_stats, N, C, sel);
+    } else {
+        if (ref_logp != nullptr)
+            hipLaunchKernelGGL((grpo_loss_kernel<true, SEL>), dim3(N), dim3(256), 0, stream, logp, ref_logp, adv, mask, beta, inv_nrows, row_scale, dlogp, kl, row_loss, row_kl, N, C, sel);
+        else
+            hipLaunchKernelGGL((grpo_loss_kernel<false, SEL>), dim3(N), dim3(256), 0, stream, logp, ref_logp, adv, mask, beta, inv_nrows, row_scale, dlogp, kl, row_loss, row_kl, N, C, sel);
+    }
+    return iadr1_check_launch(name);
+}
+}  // namespace
 extern "C" int iadr1_grpo_loss_ex(const float* logp, const float* ref_logp, const float* old_logp, const float* rollout_logp, const float* w, const float* adv,
                                   const int* mask, float beta, float cap, int level, float eps_low, float eps_high, float row_scale, int n_total_rows, float* dlogp,
                                   float* kl, float* row_loss, float* row_kl, float* w_out, float* row_stats, int N, int C, hipStream_t stream) {
-    IADR1_REQUIRE(N > 0, "grpo_loss_ex: N must be > 0 (got %d)", N);
-    IADR1_REQUIRE(C > 0, "grpo_loss_ex: C must be > 0 (got %d)", C);
-    IADR1_REQUIRE(n_total_rows >= N, "grpo_loss_ex: n_total_rows (%d) is smaller than N (%d): it is the row count of the whole step", n_total_rows, N);
-    IADR1_REQUIRE(ref_logp != nullptr || beta == 0.f, "grpo_loss_ex: ref_logp is null with beta = %g: the KL term needs the reference's log-probs (only beta == 0 runs without them)", (double)beta);
-    IADR1_REQUIRE(row_scale >= 0.f && row_scale <= 3.402823466e38f /* false for NaN and +inf */, "grpo_loss_ex: row_scale must be 0 (1 / live tokens of the row) or finite and > 0 (got %g)", (double)row_scale);
-    IADR1_REQUIRE(old_logp == nullptr || rollout_logp == nullptr, "grpo_loss_ex: old_logp and rollout_logp are both given: a reuse step takes the cached weights as w, not the rollout's log-probs");
-    IADR1_REQUIRE(w == nullptr || old_logp != nullptr, "grpo_loss_ex: w is given without old_logp (the weights belong to the clipped form)");
-    IADR1_REQUIRE(row_stats != nullptr || (old_logp == nullptr && rollout_logp == nullptr), "grpo_loss_ex: row_stats is null (the %s form writes [N, %d] partials)", old_logp ? "clip" : "IS", old_logp ? 4 : 5);
-    const float inv_nrows = 1.f / (float)n_total_rows;
-    if (old_logp != nullptr) {
-        IADR1_REQUIRE(eps_low >= 0.f && eps_low < 1.f /* false for NaN */, "grpo_loss_ex: eps_low must be in [0, 1) (got %g)", (double)eps_low);
-        IADR1_REQUIRE(eps_high >= 0.f && eps_high <= 3.402823466e38f /* false for NaN and +inf */, "grpo_loss_ex: eps_high must be finite and >= 0 (got %g)", (double)eps_high);
-        if (ref_logp != nullptr)
-            hipLaunchKernelGGL(grpo_loss_clip_kernel<true>, dim3(N), dim3(256), 0, stream, logp, old_logp, ref_logp, adv, mask, w, beta, 1.f - eps_low, 1.f + eps_high,
-                               inv_nrows, row_scale, dlogp, kl, row_loss, row_kl, row_stats, N, C);
-        else
-            hipLaunchKernelGGL(grpo_loss_clip_kernel<false>, dim3(N), dim3(256), 0, stream, logp, old_logp, ref_logp, adv, mask, w, beta, 1.f - eps_low, 1.f + eps_high,
-                               inv_nrows, row_scale, dlogp, kl, row_loss, row_kl, row_stats, N, C);
-    } else if (rollout_logp != nullptr) {
-        IADR1_REQUIRE(cap >= 1.f && cap <= 3.402823466e38f /* false for NaN and +inf */, "grpo_loss_ex: cap must be finite and >= 1 (got %g): a smaller cap would down-weight on-policy tokens", (double)cap);
-        IADR1_REQUIRE(level == 0 || level == 1, "grpo_loss_ex: unknown level %d (0 = token, 1 = sequence)", level);
-        if (ref_logp != nullptr)
-            hipLaunchKernelGGL(grpo_loss_is_kernel<true>, dim3(N), dim3(256), 0, stream, logp, ref_logp, rollout_logp, adv, mask, beta, cap, level, inv_nrows, row_scale,
-                               dlogp, kl, row_loss, row_kl, w_out, row_stats, N, C);
-        else
-            hipLaunchKernelGGL(grpo_loss_is_kernel<false>, dim3(N), dim3(256), 0, stream, logp, ref_logp, rollout_logp, adv, mask, beta, cap, level, inv_nrows, row_scale,
-                               dlogp, kl, row_loss, row_kl, w_out, row_stats, N, C);
-    } else {
-        if (ref_logp != nullptr)
-            hipLaunchKernelGGL(grpo_loss_kernel<true>, dim3(N), dim3(256), 0, stream, logp, ref_logp, adv, mask, beta, inv_nrows, row_scale, dlogp, kl, row_loss, row_kl, N, C);
-        else
-            hipLaunchKernelGGL(grpo_loss_kernel<false>, dim3(N), dim3(256), 0, stream, logp, ref_logp, adv, mask, beta, inv_nrows, row_scale, dlogp, kl, row_loss, row_kl, N, C);
-    }
-    return iadr1_check_launch("grpo_loss_ex");
+    return grpo_loss_ex_launch<false>("grpo_loss_ex", logp, ref_logp, old_logp, rollout_logp, w, adv, mask, beta, cap, level, eps_low, eps_high, row_scale, n_total_rows, dlogp, kl,
+                                      row_loss, row_kl, w_out, row_stats, N, C, nullptr, stream);
+}
+// iadr1_grpo_loss_ex with the selector.  sel == NULL: that entry point's kernels and arguments.
+extern "C" int iadr1_grpo_loss_sel(const float* logp, const float* ref_logp, const float* old_logp, const float* rollout_logp, const float* w, const float* adv,
+                                   const int* mask, float beta, float cap, int level, float eps_low, float eps_high, float row_scale, int n_total_rows, float* dlogp,
+                                   float* kl, float* row_loss, float* row_kl, float* w_out, float* row_stats, int N, int C, const int* sel, hipStream_t stream) {
+    return (sel != nullptr ? grpo_loss_ex_launch<true> : grpo_loss_ex_launch<false>)("grpo_loss_sel", logp, ref_logp, old_logp, rollout_logp, w, adv, mask, beta, cap, level, eps_low,
+                                                                                     eps_high, row_scale, n_total_rows, dlogp, kl, row_loss, row_kl, w_out, row_stats, N, C, sel, stream);
 }

@@ -12,10 +12,11 @@
 //   stage 2: grid (B): the NCHUNK*K survivors -> exact global top-K (same routine) -> rank sort -> softmax,
 //            top-p cut, inverse-CDF draw.
 //
-// ONE body per stage, stage1<LP, EX, GD> and stage2<LP, EX, GD>, behind all four entry points; a flag that is off compiles its code out:
+// ONE body per stage, stage1<LP, EX, GD, EN> and stage2<LP, EX, GD, EN>, behind all five entry points; a flag that is off compiles its code out:
 //   LP  the log-prob of the pick + whole-vocabulary sampling for top_k <= 0     iadr1_sample_topk_topp: sample_stage1/2 <0, 0, 0>; iadr1_sample_logp: sample_logp_stage1/2 <1, 0, 0>
 //   EX  a repetition penalty in front of the filter and a min_p cut behind it   iadr1_sample_ex: sample_ex_stage1/2 <1, 1, 0>
 //   GD  a per-row automaton's mask in front of everything the filter does       iadr1_sample_guided: sample_guided_stage1/2 <1, 1, 1>; without a guide sample_ex's pair
+//   EN  the entropy of the raw row's softmax beside the log-prob of the pick     iadr1_sample_ent: sample_ent_stage1/2 <1, 1, 0, 1>, with a guide sample_ent_guided_stage1/2 <1, 1, 1, 1>; without ent_out sample_guided's launch
 // The ids of two entry points are bit-equal wherever the newer one's additions are neutral, because they are this code.  The host side is one function too.
 #include "common.h"
 
@@ -278,6 +279,19 @@ __device__ __forceinline__ void guide_advance(const GuideArgs& g, int row, int s
     g.state[row] = (n >= 0 && n < g.S) ? n : st;   // a fallback pick (every allowed logit -inf) may be a disallowed id: the state then stays where it is, in range
 }
 
+// ---- EN: the entropy of the distribution the log-prob is taken under ---------------------------------------------------------------------------------------------------
+// H = -sum p ln p with p = softmax(x) over the RAW row at temperature 1: nothing suppressed, masked, penalised or filtered -- (m1, s1)'s distribution.  Stage 1 adds
+//   u1 = sum e_i (x_i - m1),  e_i = exp(x_i - m1)       (x_i = -inf skipped: 0 * -inf; every term <= 0)
+// as a fifth partial per (row, chunk), BEHIND the [B][NCHUNK][4] block.  Stage 2, with a_c = exp(m1_c - M1) (0 for an all--inf chunk):
+//   S = sum s1_c a_c,   U = sum (u1_c + (m1_c - M1) s1_c) a_c,   H = ln S - U / S
+// ln S >= 0 (the chunk that holds M1 has s1 >= 1) and U <= 0: two non-negative numbers, no cancellation.  Fixed trees, no float atomics.
+struct EntArgs {
+    float* part;        // scratch [B][NCHUNK]: u1
+    float* ent;         // [B, ld] entropies, column = the step value (logp's rule)
+    long long ld;
+    int cols;
+};
+
 // inclusive scan over the lanes of a wave
 __device__ __forceinline__ float wave_incscan(float v) {
     const int lane = threadIdx.x & 63;
@@ -289,8 +303,8 @@ __device__ __forceinline__ float wave_incscan(float v) {
     return v;
 }
 
-template <bool LP, bool EX, bool GD>     // EX and GD build on LP: the four combinations of the header are the ones that exist
-__device__ __forceinline__ void stage1(const SampleArgs& p, const LogpArgs& q, const ExArgs& e, const GuideArgs& gd) {
+template <bool LP, bool EX, bool GD, bool EN = false>     // EX, GD and EN build on LP: the six combinations of the header are the ones that exist
+__device__ __forceinline__ void stage1(const SampleArgs& p, const LogpArgs& q, const ExArgs& e, const GuideArgs& gd, const EntArgs& en = EntArgs{}) {
     __shared__ int hist[2048];
     __shared__ int sh_i[8];
     __shared__ float sh_f[16];
@@ -324,6 +338,18 @@ __device__ __forceinline__ void stage1(const SampleArgs& p, const LogpArgs& q, c
             for (int i = 0; i < ITEMS; ++i) s1 += expf(val[i] - m1);      // (padding and the suppressed slot hold -inf: they add 0)
             if (xs > -INFINITY) s1 += expf(xs - m1);
         }
+        float u1 = 0.f;
+        if constexpr (EN) {
+            // val still holds the raw slice (the suppressed slot apart: xs carries that one)
+            if (m1 > -INFINITY) {
+#pragma unroll
+                for (int i = 0; i < ITEMS; ++i) {
+                    const float d = val[i] - m1;
+                    if (val[i] > -INFINITY) u1 += expf(d) * d;
+                }
+                if (xs > -INFINITY) u1 += expf(xs - m1) * (xs - m1);
+            }
+        }
         if constexpr (GD) {
             // (m1, s1) above are the raw row's; the automaton's mask comes first of all the filter does
             const unsigned* arow = gd.allow + (long long)guide_state(gd, row) * gd.ld_allow;
@@ -354,9 +380,14 @@ __device__ __forceinline__ void stage1(const SampleArgs& p, const LogpArgs& q, c
         }
         s1 = block_sum<NT>(s1, sh_f + 8);
         sT = block_sum<NT>(sT, sh_f + 12);
+        if constexpr (EN) {
+            __shared__ float sh_u[4];       // (sh_f is used up by the four reductions above)
+            u1 = block_sum<NT>(u1, sh_u);
+        }
         if (t == 0) {
             float* o = q.part + ((long long)row * NCHUNK + chunk) * 4;
             o[0] = m1; o[1] = s1; o[2] = mT; o[3] = sT;
+            if constexpr (EN) en.part[(long long)row * NCHUNK + chunk] = u1;
         }
         if (wv) return;     // no candidate lists: stage 2 draws from the chunk masses
     }
@@ -369,16 +400,18 @@ __device__ __forceinline__ void stage1(const SampleArgs& p, const LogpArgs& q, c
     }
 }
 
-template <bool LP, bool EX, bool GD>
-__device__ __forceinline__ void commit_pick(const SampleArgs& p, const ExArgs& e, const GuideArgs& gd, int row, int st, int pick, float* lp, const float* raw, float lse) {
+template <bool LP, bool EX, bool GD, bool EN = false>
+__device__ __forceinline__ void commit_pick(const SampleArgs& p, const ExArgs& e, const GuideArgs& gd, int row, int st, int pick, float* lp, const float* raw, float lse,
+                                            float* hp = nullptr, float H = 0.f) {
     p.out[row] = pick;
     if constexpr (LP) { if (lp) *lp = *raw - lse; }
+    if constexpr (EN) { if (hp) *hp = H; }
     if constexpr (EX) mark_pick(e, row, pick);
     if constexpr (GD) guide_advance(gd, row, st, pick);
 }
 
-template <bool LP, bool EX, bool GD>
-__device__ __forceinline__ void stage2(const SampleArgs& p, const LogpArgs& q, const ExArgs& e, const GuideArgs& gd) {
+template <bool LP, bool EX, bool GD, bool EN = false>
+__device__ __forceinline__ void stage2(const SampleArgs& p, const LogpArgs& q, const ExArgs& e, const GuideArgs& gd, const EntArgs& en = EntArgs{}) {
     __shared__ int hist[2048];
     __shared__ int sh_i[8];
     __shared__ float sh_f[8];
@@ -393,6 +426,9 @@ __device__ __forceinline__ void stage2(const SampleArgs& p, const LogpArgs& q, c
     const uint32_t step = read_step(p);     // read once, at entry: the Philox counter of the whole-vocabulary draw and the log-prob column
     float* lp = (LP && q.logp != nullptr && step < (uint32_t)q.cols) ? q.logp + (long long)row * q.ld + step : nullptr;
     float lse = 0.f;    // the raw row's log-sum-exp at temperature 1 (LP)
+    float* hp = nullptr;    // where the row's entropy goes (EN): logp's column rule
+    float H = 0.f;
+    if constexpr (EN) { if (en.ent != nullptr && step < (uint32_t)en.cols) hp = en.ent + (long long)row * en.ld + step; }
     int st = 0;                         // the row's automaton state, read once: thread 0 overwrites it behind the __syncthreads() that precede every pick
     const unsigned* arow = nullptr;
     if constexpr (GD) {
@@ -405,7 +441,13 @@ __device__ __forceinline__ void stage2(const SampleArgs& p, const LogpArgs& q, c
         const float* pr = q.part + ((long long)row * NCHUNK + (have ? lane : 0)) * 4;
         const float m1 = have ? pr[0] : -INFINITY, s1 = have ? pr[1] : 0.f;
         const float M1 = wave_max(m1);
-        lse = M1 + logf(wave_sum(m1 > -INFINITY ? s1 * expf(m1 - M1) : 0.f));
+        const float S = wave_sum(m1 > -INFINITY ? s1 * expf(m1 - M1) : 0.f);
+        lse = M1 + logf(S);
+        if constexpr (EN) {
+            const float u1 = have ? en.part[(long long)row * NCHUNK + lane] : 0.f;
+            const float U = wave_sum(m1 > -INFINITY ? (u1 + (m1 - M1) * s1) * expf(m1 - M1) : 0.f);
+            H = S > 0.f ? logf(S) - U / S : 0.f;    // (S == 0: a row of -inf only has no distribution)
+        }
         if (whole_vocab(p)) {
             const float invT = 1.f / p.temperature;
             const float mT = have ? pr[2] : -INFINITY, sT = have ? pr[3] : 0.f;
@@ -484,7 +526,7 @@ __device__ __forceinline__ void stage2(const SampleArgs& p, const LogpArgs& q, c
             __syncthreads();
             if (t == 0) {
                 const int pick = sh_i[0] != 0x7fffffff ? sh_i[0] : max(sh_i[1], 0);
-                commit_pick<LP, EX, GD>(p, e, gd, row, st, pick, lp, &x[pick], lse);
+                commit_pick<LP, EX, GD, EN>(p, e, gd, row, st, pick, lp, &x[pick], lse, hp, H);
             }
             return;
         }
@@ -502,7 +544,7 @@ __device__ __forceinline__ void stage2(const SampleArgs& p, const LogpArgs& q, c
     if (p.temperature <= 0.f) {
         if (t == 0) {
             const int pick = n > 0 ? cidx[0] : 0;
-            commit_pick<LP, EX, GD>(p, e, gd, row, st, pick, lp, &x[pick], lse);
+            commit_pick<LP, EX, GD, EN>(p, e, gd, row, st, pick, lp, &x[pick], lse, hp, H);
         }
         return;
     }
@@ -518,7 +560,7 @@ __device__ __forceinline__ void stage2(const SampleArgs& p, const LogpArgs& q, c
     __syncthreads();
     if (t == 0) {
         const int pick = topk_topp_pick(p, row, sval, cval, n, EX ? e.min_p : 0.f);
-        commit_pick<LP, EX, GD>(p, e, gd, row, st, sidx[pick], lp, &sraw[pick], lse);
+        commit_pick<LP, EX, GD, EN>(p, e, gd, row, st, sidx[pick], lp, &sraw[pick], lse, hp, H);
     }
 }
 
@@ -530,6 +572,10 @@ __global__ __launch_bounds__(NT) void sample_ex_stage1(SampleArgs p, LogpArgs q,
 __global__ __launch_bounds__(NT) void sample_ex_stage2(SampleArgs p, LogpArgs q, ExArgs e) { stage2<true, true, false>(p, q, e, GuideArgs{}); }
 __global__ __launch_bounds__(NT) void sample_guided_stage1(SampleArgs p, LogpArgs q, ExArgs e, GuideArgs g) { stage1<true, true, true>(p, q, e, g); }
 __global__ __launch_bounds__(NT) void sample_guided_stage2(SampleArgs p, LogpArgs q, ExArgs e, GuideArgs g) { stage2<true, true, true>(p, q, e, g); }
+__global__ __launch_bounds__(NT) void sample_ent_stage1(SampleArgs p, LogpArgs q, ExArgs e, EntArgs n) { stage1<true, true, false, true>(p, q, e, GuideArgs{}, n); }
+__global__ __launch_bounds__(NT) void sample_ent_stage2(SampleArgs p, LogpArgs q, ExArgs e, EntArgs n) { stage2<true, true, false, true>(p, q, e, GuideArgs{}, n); }
+__global__ __launch_bounds__(NT) void sample_ent_guided_stage1(SampleArgs p, LogpArgs q, ExArgs e, GuideArgs g, EntArgs n) { stage1<true, true, true, true>(p, q, e, g, n); }
+__global__ __launch_bounds__(NT) void sample_ent_guided_stage2(SampleArgs p, LogpArgs q, ExArgs e, GuideArgs g, EntArgs n) { stage2<true, true, true, true>(p, q, e, g, n); }
 
 // iadr1_seen_init: one block per sequence zeroes its bitmap row, then ORs in the live tokens of its prompt (left-padded: columns [S - len, S)).
 __global__ __launch_bounds__(NT) void seen_init_kernel(const long long* ids, int S, const int* lengths, int G, int V, unsigned* seen, long long ld_seen) {
@@ -546,7 +592,7 @@ __global__ __launch_bounds__(NT) void seen_init_kernel(const long long* ids, int
     }
 }
 
-enum SamplerPair { PAIR_PLAIN, PAIR_LOGP, PAIR_EX, PAIR_GUIDED };
+enum SamplerPair { PAIR_PLAIN, PAIR_LOGP, PAIR_EX, PAIR_GUIDED, PAIR_ENT, PAIR_ENT_GUIDED };
 
 template <class... A>
 void launch_pair(void (*s1)(A...), void (*s2)(A...), int B, hipStream_t stream, A... a) {
@@ -554,13 +600,15 @@ void launch_pair(void (*s1)(A...), void (*s2)(A...), int B, hipStream_t stream, 
     hipLaunchKernelGGL(s2, dim3(B), dim3(NT), 0, stream, a...);
 }
 
-// The four entry points: the checks, the workspace carve-up, the argument structs and the launch, once.  `name` is the entry point's ("sample_ex": the prefix of
+// The five entry points: the checks, the workspace carve-up, the argument structs and the launch, once.  `name` is the entry point's ("sample_ex": the prefix of
 // its refusals and the middle of its workspace function's name), `pair` the kernels it launches; under the defaults of what an entry point lacks its checks pass.
 int sample_launch(const char* name, SamplerPair pair, hipStream_t stream, const float* logits, long long ld, long long* out, void* workspace, int B, int V, float temperature,
                   int top_k, float top_p, int suppress_token, unsigned long long seed, unsigned step, const unsigned* step_ptr, const unsigned long long* seed_ptr,
                   float* logp_out = nullptr, long long ld_logp = 0, int logp_cols = 0, float min_p = 0.f, float repetition_penalty = 1.f, unsigned* seen = nullptr,
                   long long ld_seen = 0, int mark_seen = 0, int* state = nullptr, const unsigned* allow = nullptr, long long ld_allow = 0, const short* trans = nullptr,
-                  long long ld_trans = 0, int S = 0) {
+                  long long ld_trans = 0, int S = 0, float* ent_out = nullptr, long long ld_ent = 0, int ent_cols = 0) {
+    IADR1_REQUIRE(ent_out == nullptr || ent_cols > 0, "%s: ent_out needs ent_cols > 0 (got %d)", name, ent_cols);
+    IADR1_REQUIRE(ent_out == nullptr || ld_ent >= ent_cols, "%s: ld_ent=%lld is less than ent_cols = %d", name, ld_ent, ent_cols);
     IADR1_REQUIRE(allow == nullptr || (state != nullptr && trans != nullptr), "%s: allow needs state [B] and trans [S, ld_trans] beside it (got state %s, trans %s)", name,
                   state ? "a buffer" : "NULL", trans ? "a buffer" : "NULL");
     IADR1_REQUIRE(allow != nullptr || (state == nullptr && trans == nullptr), "%s: state and trans must be NULL when allow is NULL: without the mask there is no automaton to advance", name);
@@ -588,11 +636,14 @@ int sample_launch(const char* name, SamplerPair pair, hipStream_t stream, const 
     LogpArgs q{part, logp_out, ld_logp, logp_cols};
     ExArgs e{min_p, repetition_penalty, seen, ld_seen, mark_seen != 0};
     GuideArgs g{state, allow, trans, ld_allow, ld_trans, S};
+    EntArgs n{part + (long long)B * NCHUNK * 4, ent_out, ld_ent, ent_cols};     // (behind the [B][NCHUNK][4] block: only iadr1_sample_ent's workspace reaches that far)
     switch (pair) {
         case PAIR_PLAIN: launch_pair(sample_stage1, sample_stage2, B, stream, p); break;
         case PAIR_LOGP: launch_pair(sample_logp_stage1, sample_logp_stage2, B, stream, p, q); break;
         case PAIR_EX: launch_pair(sample_ex_stage1, sample_ex_stage2, B, stream, p, q, e); break;
         case PAIR_GUIDED: launch_pair(sample_guided_stage1, sample_guided_stage2, B, stream, p, q, e, g); break;
+        case PAIR_ENT: launch_pair(sample_ent_stage1, sample_ent_stage2, B, stream, p, q, e, n); break;
+        case PAIR_ENT_GUIDED: launch_pair(sample_ent_guided_stage1, sample_ent_guided_stage2, B, stream, p, q, e, g, n); break;
     }
     return iadr1_check_launch(pair == PAIR_PLAIN ? "sample_topk_topp" : name);
 }
@@ -603,6 +654,7 @@ extern "C" long long iadr1_sample_workspace_bytes(int B) { return (long long)B *
 extern "C" long long iadr1_sample_logp_workspace_bytes(int B) { return (long long)B * NCHUNK * (MAXK * 8 + 16); }
 extern "C" long long iadr1_sample_ex_workspace_bytes(int B) { return iadr1_sample_logp_workspace_bytes(B); }
 extern "C" long long iadr1_sample_guided_workspace_bytes(int B) { return iadr1_sample_ex_workspace_bytes(B); }
+extern "C" long long iadr1_sample_ent_workspace_bytes(int B) { return iadr1_sample_guided_workspace_bytes(B) + (long long)B * NCHUNK * 4; }
 
 extern "C" int iadr1_sample_topk_topp(const float* logits, long long ld, long long* out, void* workspace, int B, int V, float temperature,
                                       int top_k, float top_p, int suppress_token, unsigned long long seed, unsigned step,
@@ -633,6 +685,17 @@ extern "C" int iadr1_sample_guided(const float* logits, long long ld, long long*
     // no guide: iadr1_sample_ex's own kernels, the same device code and the same bits
     return sample_launch("sample_guided", allow != nullptr ? PAIR_GUIDED : PAIR_EX, stream, logits, ld, out, workspace, B, V, temperature, top_k, top_p, suppress_token, seed, step,
                          step_ptr, seed_ptr, logp_out, ld_logp, logp_cols, min_p, repetition_penalty, seen, ld_seen, mark_seen, state, allow, ld_allow, trans, ld_trans, S);
+}
+
+extern "C" int iadr1_sample_ent(const float* logits, long long ld, long long* out, float* logp_out, long long ld_logp, int logp_cols, void* workspace, int B,
+                                int V, float temperature, int top_k, float top_p, float min_p, float repetition_penalty, unsigned* seen, long long ld_seen,
+                                int mark_seen, int suppress_token, unsigned long long seed, unsigned step, const unsigned* step_ptr,
+                                const unsigned long long* seed_ptr, int* state, const unsigned* allow, long long ld_allow, const short* trans,
+                                long long ld_trans, int S, float* ent_out, long long ld_ent, int ent_cols, hipStream_t stream) {
+    // no ent_out: iadr1_sample_guided's own launch (and through it, without a guide, iadr1_sample_ex's), the same device code and the same bits
+    const SamplerPair pair = ent_out != nullptr ? (allow != nullptr ? PAIR_ENT_GUIDED : PAIR_ENT) : (allow != nullptr ? PAIR_GUIDED : PAIR_EX);
+    return sample_launch("sample_ent", pair, stream, logits, ld, out, workspace, B, V, temperature, top_k, top_p, suppress_token, seed, step, step_ptr, seed_ptr, logp_out,
+                         ld_logp, logp_cols, min_p, repetition_penalty, seen, ld_seen, mark_seen, state, allow, ld_allow, trans, ld_trans, S, ent_out, ld_ent, ent_cols);
 }
 
 extern "C" int iadr1_seen_init(const long long* ids, int S, const int* lengths, int Bp, int G, int V, unsigned* seen, long long ld_seen, hipStream_t stream) {

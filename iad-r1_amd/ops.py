@@ -637,11 +637,13 @@ def grpo_loss_clip(logp, old_logp, ref_logp, adv, mask, beta, eps_low, eps_high,
 
 
 def grpo_loss_ex(logp, adv, mask, beta, *, ref_logp=None, old_logp=None, rollout_logp=None, w=None, cap=0.0, level="token", eps_low=0.0, eps_high=0.0, row_scale=0.0,
-                 n_total_rows=None):
+                 n_total_rows=None, sel=None):
     """iadr1_grpo_loss_ex: grpo_loss (neither old_logp nor rollout_logp), grpo_loss_is (rollout_logp, cap, level) or grpo_loss_clip (old_logp, eps_low, eps_high, w)
     with a row normaliser and an optional reference.  row_scale 0: every row's sums are divided by its live tokens (those three calls); > 0: multiplied by this
     factor instead (row_kl keeps its row mean).  ref_logp None (needs beta == 0): no KL term, kl and row_kl come back as zeros.  Returns the tuple of the call it
-    generalises: (dlogp, kl, row_loss, row_kl), + (w [N, C], row_stats [N, 5]) with rollout_logp, + (row_stats [N, 4],) with old_logp."""
+    generalises: (dlogp, kl, row_loss, row_kl), + (w [N, C], row_stats [N, 5]) with rollout_logp, + (row_stats [N, 4],) with old_logp.
+    sel [N, C] int32 of 0 / 1 (iadr1_grpo_loss_sel): the advantage part of a token's term and gradient is kept where it is 1 and dropped where it is 0; the KL
+    part, the normalisers and every statistic stay over `mask`.  None: iadr1_grpo_loss_ex itself."""
     if level not in IS_LEVELS:
         raise ValueError(f"grpo_loss_ex: level must be one of {sorted(IS_LEVELS)}, got {level!r}")
     N, C = logp.shape
@@ -652,8 +654,10 @@ def grpo_loss_ex(logp, adv, mask, beta, *, ref_logp=None, old_logp=None, rollout
     row_kl = torch.empty(N, dtype=F32, device=dev)
     w_out = torch.empty(N, C, dtype=F32, device=dev) if (rollout_logp is not None and old_logp is None) else None
     stats = torch.empty(N, 4 if old_logp is not None else 5, dtype=F32, device=dev) if (old_logp is not None or rollout_logp is not None) else None
-    hip.call("grpo_loss_ex", logp, ref_logp, old_logp, rollout_logp, w, adv, mask, float(beta), float(cap), IS_LEVELS[level], float(eps_low), float(eps_high),
-             float(row_scale), int(n_total_rows or N), dlogp, kl, row_loss, row_kl, w_out, stats, N, C)
+    if sel is not None:
+        assert sel.dtype == torch.int32 and sel.shape == (N, C) and sel.is_contiguous(), "grpo_loss_ex: sel is a contiguous [N, C] int32 tensor of 0 / 1"
+    hip.call("grpo_loss_ex" if sel is None else "grpo_loss_sel", logp, ref_logp, old_logp, rollout_logp, w, adv, mask, float(beta), float(cap), IS_LEVELS[level], float(eps_low),
+             float(eps_high), float(row_scale), int(n_total_rows or N), dlogp, kl, row_loss, row_kl, w_out, stats, N, C, *(() if sel is None else (sel,)))
     if old_logp is not None:
         return dlogp, kl, row_loss, row_kl, stats
     if rollout_logp is not None:
@@ -661,20 +665,28 @@ def grpo_loss_ex(logp, adv, mask, beta, *, ref_logp=None, old_logp=None, rollout
     return dlogp, kl, row_loss, row_kl
 
 
-_sample_ws = {}     # (B, device) -> the workspace of all four samplers: iadr1_sample_logp_workspace_bytes is the largest of their sizes
+_sample_ws = {}     # (B, device) -> the workspace of the first four samplers: iadr1_sample_logp_workspace_bytes is the largest of their sizes; (B, device, "ent") -> sample_ent's
 
 
-def _sample(name, logits32, temperature, top_k, top_p, seed, step, suppress_token, step_ptr, out, seed_ptr, logp_out=None, want_logp=False, ex=None, guide=None):
-    """The work of the four wrappers below.  name: the wrapper's, and from sample_logp onwards (the calls that take logp_out) the library call's; ex: (min_p,
-    repetition_penalty, seen, mark_seen) from sample_ex onwards; guide: (state, allow, trans) for sample_guided.  Returns (ids, logp_out or None)."""
+def _sample(name, logits32, temperature, top_k, top_p, seed, step, suppress_token, step_ptr, out, seed_ptr, logp_out=None, want_logp=False, ex=None, guide=None,
+            ent_out=None, want_ent=False):
+    """The work of the five wrappers below.  name: the wrapper's, and from sample_logp onwards (the calls that take logp_out) the library call's; ex: (min_p,
+    repetition_penalty, seen, mark_seen) from sample_ex onwards; guide: (state, allow, trans) from sample_guided onwards; ent_out / want_ent: sample_ent's, as logp_out / want_logp.  Returns (ids, logp_out or None), sample_ent
+    (ids, logp_out or None, ent_out or None)."""
     B, V = logits32.shape
-    key = (B, logits32.device)
+    ent = name == "sample_ent"
+    key = (B, logits32.device, "ent") if ent else (B, logits32.device)
     o = out if out is not None else torch.empty(B, dtype=torch.int64, device=logits32.device)
     if logp_out is None and want_logp:
         assert step_ptr is None and int(step) == 0, f"{name}: give logp_out [B, cols] when the step (the column) is not 0"
         logp_out = torch.zeros(B, 1, dtype=F32, device=logits32.device)
+    if ent_out is None and want_ent:
+        assert step_ptr is None and int(step) == 0, f"{name}: give ent_out [B, cols] when the step (the column) is not 0"
+        ent_out = torch.zeros(B, 1, dtype=F32, device=logits32.device)
+    assert ent_out is None or (ent_out.dim() == 2 and ent_out.shape[0] == B and ent_out.dtype == F32 and ent_out.stride(1) == 1), f"{name}: ent_out is [B, cols] fp32"
     if key not in _sample_ws:
-        _sample_ws[key] = torch.empty(hip.lib().iadr1_sample_logp_workspace_bytes(B), dtype=torch.uint8, device=logits32.device)
+        nbytes = hip.lib().iadr1_sample_ent_workspace_bytes(B) if ent else hip.lib().iadr1_sample_logp_workspace_bytes(B)
+        _sample_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=logits32.device)
     logp_args = () if name == "sample" else (logp_out, _ld(logp_out) if logp_out is not None else 0, logp_out.shape[1] if logp_out is not None else 0)
     min_p, repetition_penalty, seen, mark_seen = ex or (0.0, 1.0, None, False)
     assert seen is None or (seen.dim() == 2 and seen.shape[0] == B and seen.element_size() == 4 and seen.stride(1) == 1), f"{name}: seen is [B, words] of 32-bit words"
@@ -686,8 +698,9 @@ def _sample(name, logits32, temperature, top_k, top_p, seed, step, suppress_toke
     assert allow is None or (state is not None and state.dtype == torch.int32 and state.dim() == 1 and state.numel() == B and state.stride(0) == 1), f"{name}: state is [B] int32"
     guide_args = () if guide is None else (state, allow, allow.stride(0) if allow is not None else 0, trans, trans.stride(0) if trans is not None else 0, S)
     hip.call("sample_topk_topp" if name == "sample" else name, logits32, _ld(logits32), o, *logp_args, _sample_ws[key], B, V, float(temperature), int(top_k), float(top_p), *ex_args,
-             int(suppress_token), int(seed), int(step), step_ptr, seed_ptr, *guide_args)
-    return o, logp_out
+             int(suppress_token), int(seed), int(step), step_ptr, seed_ptr, *guide_args, *((ent_out, _ld(ent_out) if ent_out is not None else 0,
+                                                                                            ent_out.shape[1] if ent_out is not None else 0) if ent else ()))
+    return (o, logp_out, ent_out) if ent else (o, logp_out)
 
 
 def sample(logits32, temperature, top_k, top_p, seed, step, suppress_token=-1, step_ptr=None, out=None, seed_ptr=None):
@@ -716,6 +729,16 @@ def sample_guided(logits32, temperature, top_k, top_p, seed, step, state=None, a
     logp_out keeps sample_logp's meaning (raw logits, no mask).  All three None: bit-equal to sample_ex.  Returns (ids, logp_out or None)."""
     return _sample("sample_guided", logits32, temperature, top_k, top_p, seed, step, suppress_token, step_ptr, out, seed_ptr, logp_out, want_logp,
                    ex=(min_p, repetition_penalty, seen, mark_seen), guide=(state, allow, trans))
+
+
+def sample_ent(logits32, temperature, top_k, top_p, seed, step, state=None, allow=None, trans=None, min_p=0.0, repetition_penalty=1.0, seen=None, mark_seen=False,
+               suppress_token=-1, step_ptr=None, out=None, seed_ptr=None, logp_out=None, want_logp=True, ent_out=None, want_ent=True):
+    """iadr1_sample_ent: `sample_guided` plus H = -sum p ln p of softmax(raw row) at temperature 1 -- no suppression, mask, penalty or filter: the distribution
+    logp_out is the log-prob under.  ent_out: [B, cols] fp32, written at column step (*step_ptr when given), untouched when that is >= cols; None with want_ent: a
+    fresh [B, 1] tensor (step must then be 0 and step_ptr None); None without: sample_guided's own launch.  Ids, logp_out, seen and state are sample_guided's bits.
+    Returns (ids, logp_out or None, ent_out or None)."""
+    return _sample("sample_ent", logits32, temperature, top_k, top_p, seed, step, suppress_token, step_ptr, out, seed_ptr, logp_out, want_logp,
+                   ex=(min_p, repetition_penalty, seen, mark_seen), guide=(state, allow, trans), ent_out=ent_out, want_ent=want_ent)
 
 
 def seen_init(ids, lengths, G, V, seen):

@@ -102,8 +102,10 @@ class Rollout:
         self.trace = None           # training arena filled by the decode steps (generate(train_trace=...)); part of the captured graph
         self.decode_events = None   # bench.py sets a list: (start event, end event, decode steps, sum of prompt lengths over sequences) per call
         self.seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.sampling = dict(temperature=0.9, top_k=50, top_p=0.9, suppress=-1, eos=c.eos_token_id, pad=c.pad_token_id, logps=False, min_p=0.0, repetition_penalty=1.0, guided=False)
+        self.sampling = dict(temperature=0.9, top_k=50, top_p=0.9, suppress=-1, eos=c.eos_token_id, pad=c.pad_token_id, logps=False, min_p=0.0, repetition_penalty=1.0, guided=False,
+                             entropy=False)
         self.logps = None           # [N, max_new] fp32 log-probs of the sampled tokens (generate(return_logps=True)): column = the step counter, like out_tokens
+        self.entropy = None         # [N, max_new] fp32 entropies of the rows the tokens were sampled from (generate(return_entropy=True)): column = the step counter, like logps
         self.seen = None            # [N, ceil(V / 32)] 32-bit words (generate(repetition_penalty != 1)): bit id & 31 of word id >> 5 = the sequence has seen token id
         # generate(guide=...): the guide.TokenGuide whose tables are on the device, allow [S, ceil(V / 32)] 32-bit words and trans [S, V] int16 (uploaded once per guide
         # object), and the automaton state of every sequence [N] int32, which the sampler advances inside the captured step
@@ -176,7 +178,14 @@ class Rollout:
 
     def _sample_and_advance(self):
         s = self.sampling
-        if s["guided"]:
+        if s["entropy"]:
+            # iadr1_sample_ent: whatever of the branches below is live (a guide, the penalty, min_p, the log-probs), plus the raw row's entropy at column *step
+            pen = s["repetition_penalty"] != 1.0
+            guide = dict(state=self.g_state, allow=self.g_allow, trans=self.g_trans) if s["guided"] else {}
+            ops.sample_ent(self.logits, s["temperature"], s["top_k"], s["top_p"], 0, 0, **guide, min_p=s["min_p"], repetition_penalty=s["repetition_penalty"],
+                           seen=self.seen if pen else None, mark_seen=pen, suppress_token=s["suppress"], step_ptr=self.step, out=self.sampled, seed_ptr=self.seed_dev,
+                           logp_out=self.logps if s["logps"] else None, want_logp=False, ent_out=self.entropy, want_ent=False)
+        elif s["guided"]:
             # iadr1_sample_guided: the mask of every row's automaton state in front of the filters below, the state moved along the pick inside the second launch
             pen = s["repetition_penalty"] != 1.0
             ops.sample_guided(self.logits, s["temperature"], s["top_k"], s["top_p"], 0, 0, state=self.g_state, allow=self.g_allow, trans=self.g_trans, min_p=s["min_p"],
@@ -222,7 +231,8 @@ class Rollout:
                 ops.hip.set_decode_cus(0)
 
     def _generate(self, plan: TextPlan, img_embeds, G: int, max_new: int, temperature=0.9, top_k=50, top_p=0.9, seed=0, suppress_eos=False,
-                  stop_at_eos=True, train_carry=None, train_trace=False, shadow=None, return_logps=False, min_p=0.0, repetition_penalty=1.0, guide=None):
+                  stop_at_eos=True, train_carry=None, train_trace=False, shadow=None, return_logps=False, min_p=0.0, repetition_penalty=1.0, guide=None,
+                  return_entropy=False):
         """plan: the Bp left-padded prompts.  Returns completion ids [Bp*G, max_new] (prompt-major order: p0 x G,
         p1 x G, ...), pad after the first EOS.
         top_k <= 0: the whole vocabulary (top_p must then be 1.0).  return_logps: returns (ids, logps) -- logps [Bp*G, max_new] fp32 on the device, the
@@ -233,6 +243,9 @@ class Rollout:
         guide: a guide.TokenGuide (trl's vllm_guided_decoding_regex) -- every sequence walks the guide's automaton from its start state; tokens the current state does
         not allow are masked in front of every filter above (iadr1_sample_guided), EOS is allowed exactly where the bytes so far match the pattern, and a sequence cut at
         max_new is a prefix of a match.  The log-probs of return_logps stay those of the raw row.  suppress_eos is refused beside it: the automaton decides where EOS goes.
+        return_entropy: the return value gains, at its end, ent [Bp*G, max_new] fp32 on the device -- H = -sum p ln p of softmax(raw logits row) at temperature 1 for
+        the row every token was sampled from (iadr1_sample_ent): no suppression, guide mask, penalty or filter, the distribution the log-probs of return_logps are
+        taken under; 0 after a sequence's first EOS.  (ids, ent) or (ids, logps, ent).  Ids and log-probs are the bits of a rollout without it.
         shadow: an overlap.ChunkedRefPass -- the frozen reference's teacher-forced pass over the tokens produced so far is enqueued on ITS stream every
         `shadow.steps` decode steps, behind one event per chunk (the caller reads shadow.logp after shadow.join())."""
         e, c = self.e, self.e.cfg
@@ -264,7 +277,8 @@ class Rollout:
             self.graph = None          # (the tables and the state are kernel arguments of the captured sampler)
         sampling = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p),
                         suppress=c.eos_token_id if suppress_eos else -1, eos=c.eos_token_id if stop_at_eos and not suppress_eos else -1, pad=c.pad_token_id,
-                        logps=bool(return_logps), min_p=min_p, repetition_penalty=repetition_penalty, guided=guide is not None)
+                        logps=bool(return_logps), min_p=min_p, repetition_penalty=repetition_penalty, guided=guide is not None,
+                        entropy=bool(return_entropy))
         if repetition_penalty != 1.0 and self.seen is None:
             self.seen = torch.zeros(self.N, (c.vocab_size + 31) // 32, dtype=torch.int32, device=dev)
             self.graph = None          # (the buffer is a kernel argument of the captured sampler)
@@ -273,6 +287,11 @@ class Rollout:
                 self.logps = torch.zeros(self.N, self.max_new, dtype=F32, device=dev)
                 self.graph = None      # (the buffer is a kernel argument of the captured sampler)
             self.logps.zero_()         # columns the loop never reaches (every sequence finished early) read 0
+        if return_entropy:
+            if self.entropy is None:
+                self.entropy = torch.zeros(self.N, self.max_new, dtype=F32, device=dev)
+                self.graph = None      # (the buffer is a kernel argument of the captured sampler)
+            self.entropy.zero_()
         if sampling != self.sampling:
             self.sampling = sampling
             self.graph = None  # sampling parameters are kernel arguments frozen in the graph
@@ -393,6 +412,8 @@ class Rollout:
             state = (self.pos, self.ctx_len, self.slot, self.finished, self.step, self.cur_tok, self.out_tokens, self.cos, self.sin, self.all_done)
             if return_logps:
                 state = state + (self.logps,)
+            if return_entropy:
+                state = state + (self.entropy,)
             if repetition_penalty != 1.0:
                 state = state + (self.seen,)     # (the warm-up and the capture mark two tokens nobody sampled)
             if guide is not None:
@@ -482,13 +503,20 @@ class Rollout:
             shadow.finish(nsteps + 1, None)        # (the current stream is ordered behind the last replay)
             if shadow.trace is not None:
                 print("[iadr1 overlap] side-stream phases (ms after the start of the decode loop):", shadow.report(), flush=True)
-        if return_logps:
-            lp = self.logps[:, :max_new].clone()
-            if sampling["eos"] >= 0:       # the sampler does not know `finished`: what it drew for a finished sequence is masked here, on the device
-                is_eos = (toks == sampling["eos"]).to(torch.int32)
-                lp.masked_fill_((is_eos.cumsum(1) - is_eos) > 0, 0.0)
-            return toks, lp
-        return toks
+        if not (return_logps or return_entropy):
+            return toks
+        after_eos = None
+        if sampling["eos"] >= 0:       # the sampler does not know `finished`: what it drew for a finished sequence is masked here, on the device
+            is_eos = (toks == sampling["eos"]).to(torch.int32)
+            after_eos = (is_eos.cumsum(1) - is_eos) > 0
+        ret = (toks,)
+        for want, buf in ((return_logps, self.logps), (return_entropy, self.entropy)):
+            if want:
+                t = buf[:, :max_new].clone()
+                if after_eos is not None:
+                    t.masked_fill_(after_eos, 0.0)
+                ret = ret + (t,)
+        return ret
 
     def tokens_host(self) -> np.ndarray:
         """The last generate()'s completion ids on the host (waits for the decode replays, not for what was enqueued behind them)."""

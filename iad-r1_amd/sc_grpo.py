@@ -65,6 +65,15 @@ class GRPOArgs:
     # and rollout/is_clipped_frac.  Corrects the sampler-engine / trainer mismatch only (both sides temperature 1, unfiltered), not the temperature or top-k / top-p.
     rollout_is_cap: float = 0.0
     rollout_is_level: str = "token"
+    # the rollout also returns the entropy of the distribution every token was sampled from (iadr1_sample_ent: softmax of the raw logits row at temperature 1, the
+    # distribution rollout_logps is taken under); the step's metrics gain `entropy` (trl's key), its mean over the live completion tokens.  An APPROXIMATION of
+    # trl's number: these are the decode engine's logits under the policy that sampled, not a second forward, and they are fixed per generation where trl
+    # recomputes them on every reuse step.  Nothing in the loss or the gradients changes.
+    rollout_entropy: bool = False
+    # trl.GRPOConfig's name: the advantage term of the loss is trained only on the share rho of the live completion tokens (of all ranks) with the highest
+    # rollout entropy -- keep = entropy >= quantile(1 - rho), ties kept; the KL term stays on every live token (iadr1_grpo_loss_sel).  In [0, 1], 1 = off.  A
+    # value below 1 implies what rollout_entropy asks of the rollout; metrics entropy/threshold and entropy/kept_frac.
+    top_entropy_quantile: float = 1.0
     # trl.GRPOConfig's names and defaults (REF trl/trl/trainer/grpo_config.py; the reference's SC-GRPO path never sets them, so reuse is off by default).
     # num_iterations (mu) > 1: the caller (SCGRPOTrainer.training_step) uses every rollout for mu consecutive optimizer steps; steps 1 .. mu-1 hand the log-probs
     # iteration 0 scored back as old_logps, and the loss is the clipped surrogate -min(r A, clamp(r, 1 - epsilon, 1 + epsilon_high) A) + beta kl with
@@ -113,6 +122,10 @@ class GRPOArgs:
     def wants_rollout_logps(self) -> bool:
         return self.rollout_logps or self.rollout_is_cap > 0
 
+    @property
+    def wants_rollout_entropy(self) -> bool:
+        return self.rollout_entropy or self.top_entropy_quantile < 1.0
+
 
 def check_reuse_args(who: str, num_iterations, epsilon, epsilon_high):
     """num_iterations / epsilon / epsilon_high of GRPOArgs and GRPOConfig (`who` names the class in the message)."""
@@ -133,6 +146,53 @@ def check_sampler_args(who: str, min_p, repetition_penalty):
     if not (math.isfinite(repetition_penalty) and repetition_penalty > 0.0):
         raise ValueError(f"{who}.repetition_penalty must be finite and > 0 (got {repetition_penalty}); 1 switches it off")
     return mp
+
+
+def check_entropy_args(who: str, top_entropy_quantile, llava_rotated: bool = False):
+    """top_entropy_quantile of GRPOArgs and GRPOConfig (`who` names the class in the message).  llava_rotated: the engine scores the rotated window of
+    llava_rotate_right_padded_rows, whose columns are not the rollout's."""
+    q = top_entropy_quantile
+    if isinstance(q, bool) or not isinstance(q, (int, float)) or not (0.0 <= float(q) <= 1.0):      # (a NaN fails both compares)
+        raise ValueError(f"{who}.top_entropy_quantile must be in [0, 1] (got {q!r}): it is the share of the live completion tokens whose advantage term is trained; 1 = off")
+    if q < 1.0 and llava_rotated:
+        raise ValueError(f"{who}.top_entropy_quantile with llava_rotate_right_padded_rows: that path scores a rotated window, whose columns do not line up with the "
+                         "rollout's entropies; set llava_rotate_right_padded_rows=False to select among the completion tokens themselves")
+
+
+def entropy_keep_mask(ent, live, rho: float, group=None):
+    """trl's get_high_entropy_mask.  ent [N, C] float, live [N, C] bool (a tensor on any device, or a host array): returns (keep [N, C] bool on ent's device, tau),
+    tau = torch.quantile(live entropies of ALL ranks as float32, 1 - rho) with linear interpolation and keep = live & (ent >= tau): ties at the threshold are
+    kept.  No live token anywhere: keep is all False and tau is +inf.  group: a torch.distributed process group -- the [N, C] entropies are all-gathered with the
+    dead positions at -1 (an entropy is >= 0), N and C equal on every rank.
+    Without a group the live indices are taken from `live` on the HOST (a host-resident mask costs nothing; a device one is read back), so that forming the
+    live entropies waits for nothing on the device; with one, the other ranks' masks are only known from the gathered values (one read-back of their count)."""
+    rho = float(rho)
+    if not (0.0 <= rho <= 1.0):
+        raise ValueError(f"entropy_keep_mask: rho must be in [0, 1] (got {rho})")
+    live_h = live.detach().cpu().numpy().astype(bool) if isinstance(live, torch.Tensor) else np.asarray(live).astype(bool)
+    assert tuple(ent.shape) == live_h.shape and ent.dim() == 2, f"entropy_keep_mask: ent {tuple(ent.shape)} and live {live_h.shape} must be the same [N, C]"
+    dev = ent.device
+    ent32 = ent.detach().to(F32)
+    if dev.type == "cuda":
+        live_d = ops.h2d(live_h, dev)
+        idx = ops.h2d(np.flatnonzero(live_h).astype(np.int64), dev)
+    else:
+        live_d, idx = torch.from_numpy(live_h), torch.from_numpy(np.flatnonzero(live_h).astype(np.int64))
+    if group is None:
+        e_live = ent32.reshape(-1).index_select(0, idx)
+    else:
+        import torch.distributed as dist
+        mine = torch.where(live_d, ent32, torch.full_like(ent32, -1.0)).contiguous()
+        if dev.type == "cuda" and dist.get_backend(group) == "gloo":
+            mine = mine.cpu()
+        parts = [torch.empty_like(mine) for _ in range(dist.get_world_size(group))]
+        dist.all_gather(parts, mine, group=group)
+        every = torch.cat([t.reshape(-1) for t in parts]).to(dev)
+        e_live = every[every >= 0]
+    if e_live.numel() == 0:
+        return torch.zeros_like(live_d), torch.full((), float("inf"), dtype=F32, device=dev)
+    tau = torch.quantile(e_live, 1.0 - rho, interpolation="linear")
+    return live_d & (ent32 >= tau), tau
 
 
 LOSS_TYPES = ("grpo", "bnpo", "dr_grpo")
@@ -422,6 +482,7 @@ class SCGRPOEngine:
             raise ValueError("GRPOArgs.rollout_is_cap with llava_rotate_right_padded_rows: that path scores a rotated window, whose columns do not line up with the "
                              "rollout's log-probs; set llava_rotate_right_padded_rows=False to weight the completion tokens themselves")
         check_sampler_args("GRPOArgs", args.min_p, args.repetition_penalty)
+        check_entropy_args("GRPOArgs", args.top_entropy_quantile, llava_rotated=bool(getattr(cfg, "is_llava", False)) and args.llava_rotate_right_padded_rows)
         if args.guide is not None and args.suppress_eos:
             raise ValueError("GRPOArgs.guide with suppress_eos: the guide's automaton decides where EOS may appear; drop one of the two")
         check_reuse_args("GRPOArgs", args.num_iterations, args.epsilon, args.epsilon_high)
@@ -432,6 +493,7 @@ class SCGRPOEngine:
         if args.beta == 0:
             self._shadow_cus(0)         # a forced IADR1_OVERLAP_CUS is refused here already, not at the first rollout
         self.last_rollout_logps = None      # [N, C] device tensor of the last rollout when args.wants_rollout_logps
+        self.last_rollout_entropy = None    # [N, C] device tensor of the last rollout when args.wants_rollout_entropy
         self.pol, self.ref = Engine(policy), (Engine(ref) if ref is not None else None)
         self.dev = policy.device
         self.reducer = GradReducer(policy, group)
@@ -510,8 +572,12 @@ class SCGRPOEngine:
         toks = self._rollout.generate(plan, img_pol, a.num_generations, a.max_completion_length, temperature=0.0 if greedy else a.temperature,
                                       top_k=a.top_k, top_p=a.top_p, seed=a.seed + 1000003 * self.opt_step + 7919 * self.accum, suppress_eos=a.suppress_eos,
                                       train_carry=train_carry, train_trace=trace, shadow=shadow, return_logps=a.wants_rollout_logps,
-                                      min_p=0.0 if greedy else (a.min_p or 0.0), repetition_penalty=a.repetition_penalty, **({"guide": a.guide} if a.guide is not None else {}))
-        self.last_rollout_logps = None
+                                      min_p=0.0 if greedy else (a.min_p or 0.0), repetition_penalty=a.repetition_penalty, **({"guide": a.guide} if a.guide is not None else {}),
+                                      **({"return_entropy": True} if a.wants_rollout_entropy else {}))
+        self.last_rollout_logps, self.last_rollout_entropy = None, None
+        if a.wants_rollout_entropy:     # (the rollout's tuple ends in the entropies)
+            *toks, self.last_rollout_entropy = toks
+            toks = tuple(toks) if a.wants_rollout_logps else toks[0]
         if a.wants_rollout_logps:
             toks, self.last_rollout_logps = toks
         if shadow is not None:
@@ -572,7 +638,7 @@ class SCGRPOEngine:
 
     # ---- loss + gradients for given completions ------------------------------------------------------------------
     def loss_and_grads(self, batch, completions, rewards_per_func, backward: bool = True, last_micro_step: bool = True, vis=None, train_carry=None, defer_metrics: bool = False,
-                       ref_logps=None, policy_head=None, rollout_logps=None, old_logps=None, is_weights=None):
+                       ref_logps=None, policy_head=None, rollout_logps=None, old_logps=None, is_weights=None, rollout_entropy=None, entropy_mask=None):
         """completions: list of Bp*G id lists (prompt-major) or an [N,C] array already padded;
         rewards_per_func: [N, n_funcs] float tensor/array.  Accumulates gradients into policy.grad.
         ref_logps: [N, C] reference log-probs already computed for exactly these completions by the rollout's shadow pass (rollout(shadow_ref=True)): the
@@ -588,10 +654,17 @@ class SCGRPOEngine:
         the sampling engine against the policy that sampled does not change while its rollout is reused.
         args.beta == 0: no reference pass runs and ref_logps is not read; results "ref_logps" and "kl" are None and the metrics have no "kl".  args.loss_type other
         than "grpo" changes the row normaliser (loss_row_scale); args.mask_truncated_completions zeroes the loss-mask rows without an EOS (result "completion_mask",
-        metric completions/clipped_ratio).  Either of the first two sends the call through iadr1_grpo_loss_ex."""
+        metric completions/clipped_ratio).  Either of the first two sends the call through iadr1_grpo_loss_ex.
+        rollout_entropy: [N, >= C] entropies the rollout's sampler returned for exactly these completions (rollout with args.wants_rollout_entropy): metric
+        `entropy`, their mean over the EOS mask, and result "rollout_entropy".  With args.top_entropy_quantile < 1 they also select, once per call and from all N
+        rows of the loss mask (entropy_keep_mask, over all ranks), the tokens whose advantage term is trained (iadr1_grpo_loss_sel): metrics entropy/threshold and
+        entropy/kept_frac, result "entropy_mask" ([N, C] bool); completions without their entropies are then refused.
+        entropy_mask: a reuse iteration (old_logps=...) with args.top_entropy_quantile < 1 applies the "entropy_mask" of the call that sampled instead, and logs
+        none of the entropy metrics again."""
         a, c = self.args, self.cfg
         use_clip = old_logps is not None
         use_is = a.rollout_is_cap > 0 and not use_clip
+        use_sel = a.top_entropy_quantile < 1.0
         G = a.num_generations
         ids_p, mask_p = np.asarray(batch["input_ids"]), np.asarray(batch["attention_mask"])
         if a.max_prompt_length is not None:
@@ -613,18 +686,32 @@ class SCGRPOEngine:
                     raise ValueError(f"GRPOArgs.rollout_is_cap > 0: a reuse iteration (old_logps=...) needs is_weights, the [{N}, {C}] rollout_is_weights of the step that "
                                      f"sampled these completions: got {None if is_weights is None else tuple(is_weights.shape)}")
                 w_clip = is_weights.to(F32)
+        if use_sel and use_clip and (entropy_mask is None or tuple(entropy_mask.shape) != (N, C)):
+            raise ValueError(f"GRPOArgs.top_entropy_quantile < 1: a reuse iteration (old_logps=...) needs entropy_mask, the [{N}, {C}] entropy_mask of the step that "
+                             f"sampled these completions: got {None if entropy_mask is None else tuple(entropy_mask.shape)}")
+        if use_sel and not use_clip and (rollout_entropy is None or rollout_entropy.shape[0] != N or rollout_entropy.shape[1] < C):
+            raise ValueError(f"GRPOArgs.top_entropy_quantile < 1 needs the rollout entropies of these [{N}, {C}] completions (rollout_entropy=...): "
+                             f"got {None if rollout_entropy is None else tuple(rollout_entropy.shape)}")
         cmask = eos_completion_mask(comp, c.eos_token_id)
         # the loss mask: what the loss kernel, the row_scale and clip / IS metric denominators and the returned "completion_mask" see.  The text plans, the llava
         # rotation and completion_length keep the EOS mask (trl also zeroes the attention mask of a dropped row; the live rows do not attend to it either way)
         lmask = truncation_loss_mask(cmask, comp, c.eos_token_id) if a.mask_truncated_completions else cmask
         no_ref = a.beta == 0            # no KL term: no reference pass, nothing read through a reference pointer
-        use_ex = no_ref or a.loss_type != "grpo"
+        use_ex = no_ref or a.loss_type != "grpo" or use_sel
         # one value per call, from all N rows of the host-resident mask (not per micro-batch: results keep not depending on micro_batch_seqs)
         row_scale = loss_row_scale(a.loss_type, lmask, a.max_completion_length)
         ids = np.concatenate([np.repeat(ids_p, G, 0), comp], 1)
         mask = np.concatenate([np.repeat(mask_p, G, 0), cmask.astype(mask_p.dtype)], 1)
         S = P + C
         cmask_d = ops.h2d(lmask, self.dev)
+        ent_all = rollout_entropy[:, :C].to(F32) if (rollout_entropy is not None and not use_clip) else None
+        keep, tau, sel_d = None, None, None
+        if use_sel:
+            # one mask per call, from all N rows (not per micro-batch: results keep not depending on micro_batch_seqs) and the live tokens of all ranks
+            red = self.reducer      # (a job without an explicit group reduces over the default one)
+            grp = None if red.world <= 1 else (red.group if red.group is not None else red.dist.group.WORLD)
+            keep, tau = (entropy_mask.to(self.dev).bool(), None) if use_clip else entropy_keep_mask(ent_all, lmask.astype(bool), a.top_entropy_quantile, group=grp)
+            sel_d = keep.to(torch.int32).contiguous()
         state = {}
 
         def advantages():
@@ -737,7 +824,7 @@ class SCGRPOEngine:
                 elif use_is:
                     form = dict(rollout_logp=ro_all[r0:r1].contiguous(), cap=a.rollout_is_cap, level=a.rollout_is_level)
                 res = ops.grpo_loss_ex(lp.view(n, C), adv_d[r0:r1].contiguous(), cmask_d[r0:r1].contiguous(), a.beta, ref_logp=None if no_ref else rl.view(n, C),
-                                       row_scale=row_scale, n_total_rows=N, **form)
+                                       row_scale=row_scale, n_total_rows=N, sel=None if sel_d is None else sel_d[r0:r1].contiguous(), **form)
                 dlogp, kl, rloss, rkl = res[:4]
                 if use_clip:
                     clip_stats[r0:r1] = res[4]
@@ -791,6 +878,14 @@ class SCGRPOEngine:
             d_ = (logp_all - ro_lp) * m_
             cnt = m_.sum().clamp(min=1.0)
             means += [d_.abs().sum() / cnt, d_.abs().max(), ((torch.exp(d_) - d_ - 1.0) * m_).sum() / cnt]
+        ent_at = None
+        if ent_all is not None:
+            # the rollout's entropies over the live completion tokens (a diagnostic of the rollout: the EOS mask), and what the quantile kept of the loss mask
+            ent_at = len(means)
+            m_ = (cmask_d if lmask is cmask else ops.h2d(cmask, self.dev)).to(F32)
+            means.append((ent_all * m_).sum() / m_.sum().clamp(min=1.0))
+            if tau is not None:
+                means += [tau.to(F32), keep.sum().to(F32) / float(max(1, int(lmask.sum())))]
         dev_means = torch.stack(means)       # one device -> host read for all of them
 
         def finalize():
@@ -805,6 +900,10 @@ class SCGRPOEngine:
                 metrics.update({"rollout/logp_abs_diff_mean": lk[2], "rollout/logp_abs_diff_max": lk[3], "rollout/kl": lk[4]})
             if use_is:
                 metrics.update({"rollout/is_weight_mean": lk[5], "rollout/is_clipped_frac": lk[6]})
+            if ent_at is not None:
+                metrics.update(entropy=lk[ent_at])
+                if tau is not None:
+                    metrics.update({"entropy/threshold": lk[ent_at + 1], "entropy/kept_frac": lk[ent_at + 2]})
             return metrics
         if defer_metrics:      # the caller enqueues more work (the optimizer) before it reads the two device-side means: no idle GPU while the host comes back from the sync
             metrics["finalize"] = finalize
@@ -818,6 +917,10 @@ class SCGRPOEngine:
             out["rollout_is_weights"] = w_all
         if use_clip:
             out["old_logps"] = old_all
+        if ent_all is not None:
+            out["rollout_entropy"] = ent_all
+        if keep is not None:
+            out["entropy_mask"] = keep
         return out
 
     # ---- optimizer -------------------------------------------------------------------------------------------------
@@ -870,7 +973,7 @@ class SCGRPOEngine:
         return self._shadow_cus(n_seq) > 0
 
     def _step(self, batch, reward_fn, do_optimizer_step=True, last_micro_step=None, return_outputs=False, defer_metrics=False, completions=None, rollout_logps=None,
-              ref_logps=None, old_logps=None, is_weights=None):
+              ref_logps=None, old_logps=None, is_weights=None, rollout_entropy=None, entropy_mask=None):
         """One SC-GRPO micro-step: vision tower -> group rollout -> rewards -> reference / policy passes + backward (-> optimizer).  This is the path
         `SCGRPOTrainer.compute_loss` (the reference's API, REF:586) runs and the one bench.py times.
         reward_fn(completion_ids: np.ndarray [N,C]) -> [N, n_funcs] rewards (decode + plugin functions live with the caller, which owns the tokenizer).
@@ -882,6 +985,8 @@ class SCGRPOEngine:
         old_logps (with `completions`): a reuse iteration of args.num_iterations > 1 -- the "logps" the step that rolled these completions out returned, with its
         "ref_logps" (no reference forward here) and, with args.rollout_is_cap > 0, its "rollout_is_weights" as is_weights in place of the rollout log-probs;
         loss_and_grads then takes the clipped surrogate.
+        rollout_entropy: with `completions`, the entropies their rollout returned for these rows (args.rollout_entropy; the batched rollouts again); required with
+        args.top_entropy_quantile < 1.  entropy_mask (with old_logps): the "entropy_mask" of the step that sampled, required there on a reuse iteration.
         return_outputs: the whole loss_and_grads dict (log-probs, advantages, masks, ids, metrics) plus "completion_ids" instead of the metrics alone."""
         import time
         timing = os.environ.get("IADR1_TIMING") == "1"
@@ -897,6 +1002,12 @@ class SCGRPOEngine:
             raise ValueError("GRPOArgs.rollout_is_cap > 0: a reuse iteration (old_logps=...) needs the rollout_is_weights of the step that sampled (is_weights=...)")
         if completions is not None and old_logps is None and rollout_logps is None and self.args.rollout_is_cap > 0:
             raise ValueError("GRPOArgs.rollout_is_cap > 0: completions were handed in without their rollout log-probs (rollout_logps=...)")
+        if completions is None and (rollout_entropy is not None or entropy_mask is not None):
+            raise ValueError("rollout_entropy / entropy_mask belong to completions that were rolled out earlier: hand those in too (completions=...)")
+        if completions is not None and old_logps is not None and entropy_mask is None and self.args.top_entropy_quantile < 1:
+            raise ValueError("GRPOArgs.top_entropy_quantile < 1: a reuse iteration (old_logps=...) needs the entropy_mask of the step that sampled (entropy_mask=...)")
+        if completions is not None and old_logps is None and rollout_entropy is None and self.args.top_entropy_quantile < 1:
+            raise ValueError("GRPOArgs.top_entropy_quantile < 1: completions were handed in without their rollout entropies (rollout_entropy=...)")
         t0 = mark()
         vis = self.vision_policy(batch, save=True)
         t1 = mark()
@@ -913,6 +1024,7 @@ class SCGRPOEngine:
         ref_lp = self.shadow_logps if completions is None else ref_logps
         pol_head = self.shadow_policy_head if completions is None else None
         ro_lp = (self.last_rollout_logps if completions is None else rollout_logps) if self.args.wants_rollout_logps else None
+        ro_ent = (self.last_rollout_entropy if completions is None else rollout_entropy) if self.args.wants_rollout_entropy else None
         t2 = mark()
         # rewards are computed on the host inside loss_and_grads, after the first forward passes are in the GPU queue (in the
         # phase-timing mode they are evaluated here so that they get their own column)
@@ -921,7 +1033,8 @@ class SCGRPOEngine:
         self.last_step_traced = bool(carry and carry.get("traced"))     # the decode steps filled the completion rows of the training arena
         last = do_optimizer_step if last_micro_step is None else last_micro_step
         out = self.loss_and_grads(batch, comp, rewards, backward=True, last_micro_step=last, vis=vis, train_carry=carry, defer_metrics=defer_metrics or do_optimizer_step,
-                                  ref_logps=ref_lp, policy_head=pol_head, rollout_logps=ro_lp, old_logps=old_logps, is_weights=is_weights)
+                                  ref_logps=ref_lp, policy_head=pol_head, rollout_logps=ro_lp, old_logps=old_logps, is_weights=is_weights,
+                                  rollout_entropy=ro_ent, entropy_mask=entropy_mask)
         self.last_step_shadowed = ref_lp is not None and completions is None
         t4 = mark()
         if do_optimizer_step:

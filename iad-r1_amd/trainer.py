@@ -25,7 +25,7 @@ import torch
 
 from . import schedule
 from .params import ParamStore, VLMConfig
-from .sc_grpo import GRPOArgs, SCGRPOEngine, check_objective_args, check_reuse_args, check_sampler_args
+from .sc_grpo import GRPOArgs, SCGRPOEngine, check_entropy_args, check_objective_args, check_reuse_args, check_sampler_args
 
 
 @dataclass
@@ -51,6 +51,10 @@ class GRPOConfig:
     rollout_logps: bool = False     # log rollout/logp_abs_diff_mean|max and rollout/kl: sampled vs scored log-probs of the rollout's tokens (GRPOArgs.rollout_logps)
     rollout_is_cap: float = 0.0     # > 0 (then >= 1): weight every per-token loss term by min(exp(scored - sampled log-prob), cap); 0 = off (GRPOArgs.rollout_is_cap)
     rollout_is_level: str = "token"     # "token" | "sequence" (one weight per row, from the row's mean log-ratio)
+    rollout_entropy: bool = False   # log `entropy`: the mean entropy of the distributions the rollout's tokens were sampled from, out of the sampler (GRPOArgs.rollout_entropy)
+    # trl.GRPOConfig's name: train the advantage term only on this share of the live completion tokens, the ones with the highest rollout entropy; in [0, 1],
+    # 1 = off; below 1 implies rollout_entropy (GRPOArgs.top_entropy_quantile)
+    top_entropy_quantile: float = 1.0
     # trl.GRPOConfig's names and defaults.  num_iterations (mu) > 1: every rollout serves mu consecutive optimizer steps (training_step); steps 1 .. mu-1 run no
     # rollout, no reward function and no reference forward, and take the clipped surrogate -min(r A, clamp(r, 1 - epsilon, 1 + epsilon_high) A) + beta kl against
     # the log-probs scored at step 0 (GRPOArgs.num_iterations).  The reference's scripts never set it: 1 is today's step.
@@ -349,6 +353,7 @@ class SCGRPOTrainer:
         check_reuse_args("GRPOConfig", args.num_iterations, args.epsilon, args.epsilon_high)
         check_sampler_args("GRPOConfig", args.min_p, args.repetition_penalty)
         check_objective_args("GRPOConfig", args.loss_type)
+        check_entropy_args("GRPOConfig", args.top_entropy_quantile)
         guide_dfa = None
         if args.vllm_guided_decoding_regex is not None:     # a pattern error surfaces here, before any weight is loaded
             from .guide import compile_regex
@@ -431,6 +436,7 @@ class SCGRPOTrainer:
         self.engine = SCGRPOEngine(self.cfg, self.policy, self.ref, GRPOArgs(
             num_generations=args.num_generations, max_prompt_length=args.max_prompt_length, max_completion_length=args.max_completion_length,
             beta=args.beta, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, min_p=args.min_p, repetition_penalty=args.repetition_penalty, guide=self.guide, rollout_logps=args.rollout_logps, rollout_is_cap=args.rollout_is_cap, rollout_is_level=args.rollout_is_level,
+            rollout_entropy=args.rollout_entropy, top_entropy_quantile=args.top_entropy_quantile,
             num_iterations=args.num_iterations, epsilon=args.epsilon, epsilon_high=args.epsilon_high, loss_type=args.loss_type, scale_rewards=args.scale_rewards,
             mask_truncated_completions=args.mask_truncated_completions, learning_rate=args.learning_rate, weight_decay=args.weight_decay,
             adam_beta1=args.adam_beta1, adam_beta2=args.adam_beta2, adam_epsilon=args.adam_epsilon, max_grad_norm=args.max_grad_norm,
@@ -495,7 +501,7 @@ class SCGRPOTrainer:
 
     # ---- reference API ---------------------------------------------------------------------------------------------
     def compute_loss(self, model, inputs, return_outputs=False, num_items_in_batch=None, last_micro_step=True, _defer=False, _prepared=None, _batch=None, _completions=None,
-                     _rollout_logps=None, _reuse=None):
+                     _rollout_logps=None, _reuse=None, _rollout_entropy=None):
         """One SC-GRPO micro-step on `inputs` (list of dataset rows).  Returns the loss value; gradients are
         accumulated inside the engine (there is no autograd graph to hand back).
         _defer (training_step, last micro-batch): returns a callable that yields the loss once called -- the two device-side means (loss, KL) are then read
@@ -509,7 +515,7 @@ class SCGRPOTrainer:
         if _reuse is not None:
             out = self.engine.step(_reuse["batch"], lambda comp: _reuse["rewards_per_func"], do_optimizer_step=False, last_micro_step=last_micro_step, return_outputs=True,
                                    defer_metrics=_defer, completions=_reuse["completions"], ref_logps=_reuse["ref_logps"], old_logps=_reuse["old_logps"],
-                                   is_weights=_reuse["is_weights"])
+                                   is_weights=_reuse["is_weights"], entropy_mask=_reuse["entropy_mask"])
             return self._finish_metrics(out["metrics"], _defer)
         if _batch is not None:          # training_step already built it (and rolled the completions out with the other micro-batches of the step: _completions)
             batch = _batch
@@ -521,16 +527,18 @@ class SCGRPOTrainer:
         # the engine's whole micro-step (SCGRPOEngine.step): vision tower once per image, rollout whose prefill / decode steps double as the policy's
         # training forward when the micro-batch holds whole groups, rewards evaluated on the host while the reference pass is in the GPU queue
         out = self.engine.step(batch, lambda comp: self._rewards(inputs, comp), do_optimizer_step=False, last_micro_step=last_micro_step, return_outputs=True, defer_metrics=_defer,
-                               completions=_completions, rollout_logps=_rollout_logps)
+                               completions=_completions, rollout_logps=_rollout_logps, rollout_entropy=_rollout_entropy)
         m = out["metrics"]
         if self.args.num_iterations > 1:
             # device tensors as the step returned them (no host round trip), cut to the longest completion of these rows like the batched rollout's (trim_completions)
             # (not for the LLaVA families: their rotated scoring window depends on the row length, REF:516-567, so a reuse step keeps the columns step 0 scored)
             comp = out["completion_ids"] if self.cfg.is_llava else trim_completions(out["completion_ids"], self.cfg.eos_token_id)
             c = comp.shape[1]
-            w = out.get("rollout_is_weights")
+            w, ent, keep = out.get("rollout_is_weights"), out.get("rollout_entropy"), out.get("entropy_mask")
             self._generation.append({"batch": batch, "completions": comp, "old_logps": out["logps"][:, :c].contiguous(), "ref_logps": None if out["ref_logps"] is None else out["ref_logps"][:, :c].contiguous(),
-                                     "rewards_per_func": out["rewards_per_func"], "is_weights": None if w is None else w[:, :c].contiguous()})
+                                     "rewards_per_func": out["rewards_per_func"], "is_weights": None if w is None else w[:, :c].contiguous(),
+                                     # the rollout's entropies are fixed per generation: the reuse steps apply the mask step 0 drew from them
+                                     "rollout_entropy": None if ent is None else ent[:, :c].contiguous(), "entropy_mask": None if keep is None else keep[:, :c].contiguous()})
         self._metrics["completion_length"].append(m["completion_length"])
         if "completions/clipped_ratio" in m:        # (mask_truncated_completions: a job-wide option, so every rank logs the same keys)
             self._metrics["completions/clipped_ratio"].append(m["completions/clipped_ratio"])
@@ -548,7 +556,8 @@ class SCGRPOTrainer:
             if "kl" in m:       # absent with beta == 0, on every rank alike
                 self._metrics["kl"].append(m["kl"])
             for k in ("rollout/logp_abs_diff_mean", "rollout/logp_abs_diff_max", "rollout/kl", "rollout/is_weight_mean", "rollout/is_clipped_frac",
-                      "clip_ratio/low_mean", "clip_ratio/high_mean", "clip_ratio/region_mean", "policy/ratio_mean", "policy/logp_abs_diff_max"):
+                      "clip_ratio/low_mean", "clip_ratio/high_mean", "clip_ratio/region_mean", "policy/ratio_mean", "policy/logp_abs_diff_max", "entropy", "entropy/threshold",
+                      "entropy/kept_frac"):
                 if k in m:
                     self._metrics[k].append(m[k])
             return m["loss"]
@@ -587,7 +596,7 @@ class SCGRPOTrainer:
             return losses
         self._generation = []
         last = len(micro_batches) - 1
-        ready = comps = lps = None
+        ready = comps = lps = ents = None
         rows_total = sum(len(mb) for mb in micro_batches) * self.args.num_generations
         if self.args.batch_rollouts and len(micro_batches) > 1 and rows_total <= 64:
             # (<= 64 sequences: one 64-row tile of the decode GEMMs -- beyond that a decode step streams the weights once per tile and batching buys nothing, while
@@ -600,15 +609,17 @@ class SCGRPOTrainer:
                 G = self.args.num_generations
                 toks = self.engine.rollout(both)
                 all_lp = self.engine.last_rollout_logps      # None unless GRPOConfig.rollout_logps or rollout_is_cap
-                comps, lps, r = [], [], 0
+                all_ent = self.engine.last_rollout_entropy   # None unless GRPOConfig.rollout_entropy or top_entropy_quantile < 1
+                comps, lps, ents, r = [], [], [], 0
                 for b in ready:
                     n = len(b["input_ids"]) * G
                     comps.append(trim_completions(toks[r: r + n], self.cfg.eos_token_id))
                     lps.append(None if all_lp is None else all_lp[r: r + n, : comps[-1].shape[1]].contiguous())
+                    ents.append(None if all_ent is None else all_ent[r: r + n, : comps[-1].shape[1]].contiguous())
                     r += n
         losses = [self.compute_loss(None, inputs, last_micro_step=(k == last), _defer=(k == last), _prepared=None if (prepared is None or ready is not None) else prepared[k],
                                     _batch=None if ready is None else ready[k], _completions=None if comps is None else comps[k],
-                                    _rollout_logps=None if comps is None else lps[k])
+                                    _rollout_logps=None if comps is None else lps[k], _rollout_entropy=None if comps is None else ents[k])
                   for k, inputs in enumerate(micro_batches)]
         self.engine.optimizer_step()
         losses[last] = losses[last]()       # the last micro-batch's loss / KL means are read after the optimizer launches are in the queue

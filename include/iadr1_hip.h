@@ -331,6 +331,18 @@ int iadr1_grpo_loss_ex(const float* logp, const float* ref_logp /* may be NULL *
                        const float* w /* may be NULL */, const float* adv, const int* mask, float beta, float cap, int level, float eps_low, float eps_high,
                        float row_scale, int n_total_rows, float* dlogp, float* kl /* may be NULL */, float* row_loss, float* row_kl, float* w_out /* may be NULL */,
                        float* row_stats, int N, int C, iadr1_stream_t stream);
+/* grpo_loss_sel: iadr1_grpo_loss_ex with a per-token selector on the ADVANTAGE term -- trl's top_entropy_quantile, which trains the policy term on the
+ * highest-entropy share of the completion tokens only (trl's GRPOTrainer get_high_entropy_mask; the mask multiplies per_token_loss1 / per_token_loss2 there and
+ * the KL term is added behind it).  sel: [N, C] int32 of 0 / 1 in the layout of mask.  With q_i = sel_i and s_i = A (plain and IS forms) or min(r_i A, rc_i A)
+ * (clipped form):  t_i = -(q_i s_i - beta kl_i),  and g_i is iadr1_grpo_loss_ex's with its advantage part multiplied by q_i.  Everything else is that call's and
+ * stays over the LIVE tokens (mask): the KL part of t_i and g_i, kl, row_kl, the row normaliser (cnt, row_scale), the sequence-level importance ratio, w_out and
+ * every column of row_stats (the clip counts included).  The gate is a select in front of the advantage operand, never a product by 1.0: with sel all ones
+ * every output is bit-equal to iadr1_grpo_loss_ex's.  sel == NULL: iadr1_grpo_loss_ex's own kernels and arguments.  Refusals: iadr1_grpo_loss_ex's, with the
+ * prefix "grpo_loss_sel:". */
+int iadr1_grpo_loss_sel(const float* logp, const float* ref_logp /* may be NULL */, const float* old_logp /* may be NULL */, const float* rollout_logp /* may be NULL */,
+                        const float* w /* may be NULL */, const float* adv, const int* mask, float beta, float cap, int level, float eps_low, float eps_high,
+                        float row_scale, int n_total_rows, float* dlogp, float* kl /* may be NULL */, float* row_loss, float* row_kl, float* w_out /* may be NULL */,
+                        float* row_stats, int N, int C, const int* sel /* may be NULL */, iadr1_stream_t stream);
 
 /* ---- optimizer (HF Trainer default AdamW + clip_grad_norm_, TF:trainer.py:1168) ------------------------------- */
 /* out[0] = sum(g^2), deterministic (fixed-order two-stage reduction; scratch = 2048 floats) so that data-parallel
@@ -347,9 +359,9 @@ int iadr1_sample_topk_topp(const float* logits, long long ld, long long* out, vo
                            const unsigned* step_ptr, const unsigned long long* seed_ptr, iadr1_stream_t stream);
 /* step_ptr / seed_ptr: optional device-resident step counter / seed that replace the scalar arguments (a captured hipGraph freezes
  * kernel arguments: the rollout replays one graph for every decode step of every optimizer step). */
-/* The four entry points of this section are one device body per stage behind four kernel pairs (csrc/sample.hip: stage1 / stage2 <LP, EX, GD>, each entry point launches
+/* The five entry points of this section are one device body per stage behind six kernel pairs (csrc/sample.hip: stage1 / stage2 <LP, EX, GD, EN>, each entry point launches
  * its own instantiations) and one host function: two of them give the same bits wherever what the newer one adds is neutral, and every refusal carries its entry point's
- * prefix ("sample:", "sample_logp:", "sample_ex:", "sample_guided:").  top_k <= 0 means 64 candidates in iadr1_sample_topk_topp and the whole vocabulary from
+ * prefix ("sample:", "sample_logp:", "sample_ex:", "sample_guided:", "sample_ent:").  top_k <= 0 means 64 candidates in iadr1_sample_topk_topp and the whole vocabulary from
  * iadr1_sample_logp onwards. */
 /* iadr1_sample_logp: the same sampler, plus what vLLM returns beside the token ids and what its evaluation callers sample with.
  *   top_k in 1..64: filter semantics, Philox stream and token ids of iadr1_sample_topk_topp, bit for bit (greedy, suppress_token, step_ptr, seed_ptr included).
@@ -416,6 +428,28 @@ int iadr1_sample_guided(const float* logits, long long ld, long long* out, float
                         int mark_seen, int suppress_token, unsigned long long seed, unsigned step, const unsigned* step_ptr,
                         const unsigned long long* seed_ptr, int* state, const unsigned* allow, long long ld_allow, const short* trans,
                         long long ld_trans, int S, iadr1_stream_t stream);
+/* iadr1_sample_ent: iadr1_sample_guided plus the entropy of the distribution every token was sampled from -- what trl logs as `entropy` and ranks tokens by for
+ * top_entropy_quantile -- out of the slices stage 1 already holds in registers.
+ *   ent_out: [B, ld_ent] fp32.  ent_out[row * ld_ent + col] = H(row) = -sum_v p_v ln p_v,  p = softmax(logits[row, :]) over the RAW fp32 row at temperature 1: no
+ *     suppressed token (its logit counts), no guide mask, no repetition penalty, no temperature, no top-k / top-p / min_p -- the distribution logp_out is the
+ *     log-prob under.  Logits equal to -inf contribute 0; a row of -inf only gives 0.  col = *step_ptr (else step), nothing is written when col >= ent_cols: the
+ *     column rule of logp_out.
+ *   How: per (row, chunk) stage 1 adds  u1 = sum e_i (x_i - m1),  e_i = exp(x_i - m1)  to the partials (m1, s1); stage 2 merges, with a_c = exp(m1_c - M1),
+ *     S = sum s1_c a_c,  U = sum (u1_c + (m1_c - M1) s1_c) a_c,  H = ln S - U / S.  ln S >= 0 and U <= 0: sums of same-signed terms, no cancellation; fixed trees
+ *     (<= 20 serial adds, 6 shuffle levels, 3 adds over the waves, 6 shuffle levels over the chunks), no float atomics: run-to-run bit-identical.
+ *   ids, logp_out, seen and state are bit-equal to iadr1_sample_guided on the same arguments (the same device code).
+ *   ent_out == NULL: iadr1_sample_guided's own launch (without a guide iadr1_sample_ex's): the same kernels, the same bits; that call's workspace is enough.
+ *   Otherwise the <1, 1, 0, 1> pair without a guide and the <1, 1, 1, 1> pair with one; workspace: iadr1_sample_ent_workspace_bytes(B) = the guided size +
+ *     B * 32 * 4 bytes (the fifth partial lies BEHIND everything the other entry points use).
+ *   Refused on the host, before any launch, one message each (prefix "sample_ent:"): ent_out with ent_cols <= 0; ent_out with ld_ent < ent_cols; and everything
+ *     iadr1_sample_guided refuses (top_k <= 0 with top_p < 1 included).
+ *   Same Philox stream, step_ptr / seed_ptr, two launches.  No allocation, no host sync: legal under hipGraph capture. */
+long long iadr1_sample_ent_workspace_bytes(int B);
+int iadr1_sample_ent(const float* logits, long long ld, long long* out, float* logp_out, long long ld_logp, int logp_cols, void* workspace, int B,
+                     int V, float temperature, int top_k, float top_p, float min_p, float repetition_penalty, unsigned* seen, long long ld_seen,
+                     int mark_seen, int suppress_token, unsigned long long seed, unsigned step, const unsigned* step_ptr,
+                     const unsigned long long* seed_ptr, int* state, const unsigned* allow, long long ld_allow, const short* trans,
+                     long long ld_trans, int S, float* ent_out, long long ld_ent, int ent_cols, iadr1_stream_t stream);
 /* iadr1_seen_init: the seen bitmap of a rollout's Bp * G sequences from its Bp left-padded prompts ids [Bp, S]: zeroes rows [0, Bp * G) (ld_seen words each) and,
  * for sequence r, sets the bits of the lengths[r / G] live tokens of prompt row r / G (columns [S - len, S): image placeholder ids included, left padding
  * not).  Ids outside [0, V) are ignored, never written.  One launch; integer atomic OR on global memory. */

@@ -95,6 +95,11 @@ def build_parser():
                    help="> 0 (then >= 1): weight every per-token loss term by min(exp(scored - sampled log-prob), cap), the truncated importance weight against the "
                         "rollout's log-probs (e.g. with --decode_weights fp8); 0 = off")
     p.add_argument("--rollout_is_level", default="token", choices=["token", "sequence"], help="one weight per token, or one per completion from its mean log-ratio")
+    p.add_argument("--rollout_entropy", nargs="?", default=False, const=True, type=lambda v: str(v).lower() in ("1", "true", "yes"),
+                   help="log entropy: the mean entropy of the distributions the rollout's tokens were sampled from (raw logits, temperature 1), computed inside the sampler")
+    p.add_argument("--top_entropy_quantile", type=float, default=1.0,
+                   help="train the advantage term only on this share of the live completion tokens, the ones with the highest rollout entropy (trl's name); in [0, 1], "
+                        "1 = off; below 1 implies --rollout_entropy")
     p.add_argument("--num_iterations", type=int, default=1,
                    help="optimizer steps per rollout (trl's mu): steps after the first of a generation score the same completions again under the clipped surrogate")
     p.add_argument("--epsilon", type=float, default=0.2, help="lower clip bound 1 - epsilon of the policy ratio (and the upper one unless --epsilon_high); read when --num_iterations > 1")

@@ -589,51 +589,45 @@ def linear_logprob_dlogits(h, w, targets, lse, g, out=None):
     return dl
 
 
-def grpo_loss(logp, ref_logp, adv, mask, beta, n_total_rows=None):
+IS_LEVELS = {"token": 0, "sequence": 1}
+
+
+def _is_level(name, level):
+    if level not in IS_LEVELS:
+        raise ValueError(f"{name}: level must be one of {sorted(IS_LEVELS)}, got {level!r}")
+    return IS_LEVELS[level]
+
+
+def _grpo_loss(name, head, logp, w_out=False, stats_cols=0, both_slots=False, tail=()):
+    """The work of the four wrappers below: allocates the outputs and calls iadr1_<name>(*head, dlogp, kl, row_loss, row_kl, <w_out, row_stats>, N, C, *tail).
+    w_out / stats_cols: whether the call's form writes w [N, C] / how many columns its row_stats has (0: none).  both_slots: the entry point takes w_out and
+    row_stats whatever the form (None for the one the form lacks); otherwise it takes exactly those its form writes.
+    Returns (dlogp, kl, row_loss, row_kl) + those of (w, row_stats) that exist."""
     N, C = logp.shape
     dev = logp.device
-    dlogp = torch.empty(N, C, dtype=F32, device=dev)
-    kl = torch.empty(N, C, dtype=F32, device=dev)
-    row_loss = torch.empty(N, dtype=F32, device=dev)
-    row_kl = torch.empty(N, dtype=F32, device=dev)
-    hip.call("grpo_loss", logp, ref_logp, adv, mask, float(beta), int(n_total_rows or N), dlogp, kl, row_loss, row_kl, N, C)
-    return dlogp, kl, row_loss, row_kl
+    out = [torch.empty(N, C, dtype=F32, device=dev), torch.empty(N, C, dtype=F32, device=dev), torch.empty(N, dtype=F32, device=dev), torch.empty(N, dtype=F32, device=dev)]
+    extra = [torch.empty(N, C, dtype=F32, device=dev) if w_out else None, torch.empty(N, stats_cols, dtype=F32, device=dev) if stats_cols else None]
+    given = [t for t in extra if t is not None]
+    hip.call(name, *head, *out, *(extra if both_slots else given), N, C, *tail)
+    return (*out, *given)
 
 
-IS_LEVELS = {"token": 0, "sequence": 1}
+def grpo_loss(logp, ref_logp, adv, mask, beta, n_total_rows=None):
+    return _grpo_loss("grpo_loss", (logp, ref_logp, adv, mask, float(beta), int(n_total_rows or logp.shape[0])), logp)
 
 
 def grpo_loss_is(logp, ref_logp, rollout_logp, adv, mask, beta, cap, level="token", n_total_rows=None):
     """iadr1_grpo_loss_is: grpo_loss with the truncated importance weight min(exp(logp - rollout_logp), cap) per token ("token") or per row ("sequence").
     Returns (dlogp, kl, row_loss, row_kl, w [N, C], row_stats [N, 5]); the columns of row_stats are named in include/iadr1_hip.h."""
-    if level not in IS_LEVELS:
-        raise ValueError(f"grpo_loss_is: level must be one of {sorted(IS_LEVELS)}, got {level!r}")
-    N, C = logp.shape
-    dev = logp.device
-    dlogp = torch.empty(N, C, dtype=F32, device=dev)
-    kl = torch.empty(N, C, dtype=F32, device=dev)
-    row_loss = torch.empty(N, dtype=F32, device=dev)
-    row_kl = torch.empty(N, dtype=F32, device=dev)
-    w = torch.empty(N, C, dtype=F32, device=dev)
-    stats = torch.empty(N, 5, dtype=F32, device=dev)
-    hip.call("grpo_loss_is", logp, ref_logp, rollout_logp, adv, mask, float(beta), float(cap), IS_LEVELS[level], int(n_total_rows or N), dlogp, kl, row_loss, row_kl,
-             w, stats, N, C)
-    return dlogp, kl, row_loss, row_kl, w, stats
+    return _grpo_loss("grpo_loss_is", (logp, ref_logp, rollout_logp, adv, mask, float(beta), float(cap), _is_level("grpo_loss_is", level),
+                                        int(n_total_rows or logp.shape[0])), logp, w_out=True, stats_cols=5)
 
 
 def grpo_loss_clip(logp, old_logp, ref_logp, adv, mask, beta, eps_low, eps_high, w=None, n_total_rows=None):
     """iadr1_grpo_loss_clip: the clipped surrogate -min(r A, clamp(r, 1 - eps_low, 1 + eps_high) A) + beta kl with r = exp(logp - old_logp), every per-token term
     times w [N, C] when given.  Returns (dlogp, kl, row_loss, row_kl, row_stats [N, 4]); the columns of row_stats are named in include/iadr1_hip.h."""
-    N, C = logp.shape
-    dev = logp.device
-    dlogp = torch.empty(N, C, dtype=F32, device=dev)
-    kl = torch.empty(N, C, dtype=F32, device=dev)
-    row_loss = torch.empty(N, dtype=F32, device=dev)
-    row_kl = torch.empty(N, dtype=F32, device=dev)
-    stats = torch.empty(N, 4, dtype=F32, device=dev)
-    hip.call("grpo_loss_clip", logp, old_logp, ref_logp, adv, mask, w, float(beta), float(eps_low), float(eps_high), int(n_total_rows or N), dlogp, kl, row_loss,
-             row_kl, stats, N, C)
-    return dlogp, kl, row_loss, row_kl, stats
+    return _grpo_loss("grpo_loss_clip", (logp, old_logp, ref_logp, adv, mask, w, float(beta), float(eps_low), float(eps_high), int(n_total_rows or logp.shape[0])), logp,
+                      stats_cols=4)
 
 
 def grpo_loss_ex(logp, adv, mask, beta, *, ref_logp=None, old_logp=None, rollout_logp=None, w=None, cap=0.0, level="token", eps_low=0.0, eps_high=0.0, row_scale=0.0,
@@ -644,25 +638,12 @@ def grpo_loss_ex(logp, adv, mask, beta, *, ref_logp=None, old_logp=None, rollout
     generalises: (dlogp, kl, row_loss, row_kl), + (w [N, C], row_stats [N, 5]) with rollout_logp, + (row_stats [N, 4],) with old_logp.
     sel [N, C] int32 of 0 / 1 (iadr1_grpo_loss_sel): the advantage part of a token's term and gradient is kept where it is 1 and dropped where it is 0; the KL
     part, the normalisers and every statistic stay over `mask`.  None: iadr1_grpo_loss_ex itself."""
-    if level not in IS_LEVELS:
-        raise ValueError(f"grpo_loss_ex: level must be one of {sorted(IS_LEVELS)}, got {level!r}")
-    N, C = logp.shape
-    dev = logp.device
-    dlogp = torch.empty(N, C, dtype=F32, device=dev)
-    kl = torch.empty(N, C, dtype=F32, device=dev)
-    row_loss = torch.empty(N, dtype=F32, device=dev)
-    row_kl = torch.empty(N, dtype=F32, device=dev)
-    w_out = torch.empty(N, C, dtype=F32, device=dev) if (rollout_logp is not None and old_logp is None) else None
-    stats = torch.empty(N, 4 if old_logp is not None else 5, dtype=F32, device=dev) if (old_logp is not None or rollout_logp is not None) else None
+    head = (logp, ref_logp, old_logp, rollout_logp, w, adv, mask, float(beta), float(cap), _is_level("grpo_loss_ex", level), float(eps_low), float(eps_high),
+            float(row_scale), int(n_total_rows or logp.shape[0]))
     if sel is not None:
-        assert sel.dtype == torch.int32 and sel.shape == (N, C) and sel.is_contiguous(), "grpo_loss_ex: sel is a contiguous [N, C] int32 tensor of 0 / 1"
-    hip.call("grpo_loss_ex" if sel is None else "grpo_loss_sel", logp, ref_logp, old_logp, rollout_logp, w, adv, mask, float(beta), float(cap), IS_LEVELS[level], float(eps_low),
-             float(eps_high), float(row_scale), int(n_total_rows or N), dlogp, kl, row_loss, row_kl, w_out, stats, N, C, *(() if sel is None else (sel,)))
-    if old_logp is not None:
-        return dlogp, kl, row_loss, row_kl, stats
-    if rollout_logp is not None:
-        return dlogp, kl, row_loss, row_kl, w_out, stats
-    return dlogp, kl, row_loss, row_kl
+        assert sel.dtype == torch.int32 and sel.shape == logp.shape and sel.is_contiguous(), "grpo_loss_ex: sel is a contiguous [N, C] int32 tensor of 0 / 1"
+    return _grpo_loss("grpo_loss_ex" if sel is None else "grpo_loss_sel", head, logp, w_out=rollout_logp is not None and old_logp is None,
+                      stats_cols=4 if old_logp is not None else 5 if rollout_logp is not None else 0, both_slots=True, tail=() if sel is None else (sel,))
 
 
 _sample_ws = {}     # (B, device) -> the workspace of the first four samplers: iadr1_sample_logp_workspace_bytes is the largest of their sizes; (B, device, "ent") -> sample_ent's

@@ -83,7 +83,7 @@ class GRPOArgs:
     epsilon_high: float | None = None
     # how a step's per-token terms are normalised (REF trl/trl/trainer/grpo_trainer.py:1212-1219): "grpo" = every row a mean over its own live tokens, then the mean
     # over rows; "bnpo" = the sum over the step's rows divided by their live tokens; "dr_grpo" = divided by rows x max_completion_length.  The default is "grpo", not
-    # trl's "bnpo": that is what the reference's trainer computes (sc_grpo_trainer.py:796-798).  Anything but "grpo" goes through iadr1_grpo_loss_ex.
+    # trl's "bnpo": that is what the reference's trainer computes (sc_grpo_trainer.py:796-798).  Anything but "grpo" is a row_scale > 0 of iadr1_grpo_loss_ex (loss_row_scale).
     loss_type: str = "grpo"
     # False: advantages = reward - group mean, not divided by the group's std + 1e-4 (REF ...grpo_trainer.py:1080-1082); reward_std is logged either way
     scale_rewards: bool = True
@@ -654,7 +654,7 @@ class SCGRPOEngine:
         the sampling engine against the policy that sampled does not change while its rollout is reused.
         args.beta == 0: no reference pass runs and ref_logps is not read; results "ref_logps" and "kl" are None and the metrics have no "kl".  args.loss_type other
         than "grpo" changes the row normaliser (loss_row_scale); args.mask_truncated_completions zeroes the loss-mask rows without an EOS (result "completion_mask",
-        metric completions/clipped_ratio).  Either of the first two sends the call through iadr1_grpo_loss_ex.
+        metric completions/clipped_ratio).  Whatever the options, the loss is one iadr1_grpo_loss_ex call per micro-batch (iadr1_grpo_loss_sel with a selector).
         rollout_entropy: [N, >= C] entropies the rollout's sampler returned for exactly these completions (rollout with args.wants_rollout_entropy): metric
         `entropy`, their mean over the EOS mask, and result "rollout_entropy".  With args.top_entropy_quantile < 1 they also select, once per call and from all N
         rows of the loss mask (entropy_keep_mask, over all ranks), the tokens whose advantage term is trained (iadr1_grpo_loss_sel): metrics entropy/threshold and
@@ -697,7 +697,6 @@ class SCGRPOEngine:
         # rotation and completion_length keep the EOS mask (trl also zeroes the attention mask of a dropped row; the live rows do not attend to it either way)
         lmask = truncation_loss_mask(cmask, comp, c.eos_token_id) if a.mask_truncated_completions else cmask
         no_ref = a.beta == 0            # no KL term: no reference pass, nothing read through a reference pointer
-        use_ex = no_ref or a.loss_type != "grpo" or use_sel
         # one value per call, from all N rows of the host-resident mask (not per micro-batch: results keep not depending on micro_batch_seqs)
         row_scale = loss_row_scale(a.loss_type, lmask, a.max_completion_length)
         ids = np.concatenate([np.repeat(ids_p, G, 0), comp], 1)
@@ -816,29 +815,20 @@ class SCGRPOEngine:
                 if si == 0 and shadowed:
                     self._shadow.join()          # the tail chunk of the shadow pass ran next to the policy's lm_head; everything after this reads its log-probs
                 rl = ref_logps[r0:r1].contiguous()
-            if use_ex:
-                # beta == 0 or another loss_type than "grpo": the same three forms through iadr1_grpo_loss_ex
-                form = {}
-                if use_clip:
-                    form = dict(old_logp=old_all[r0:r1].contiguous(), w=None if w_clip is None else w_clip[r0:r1].contiguous(), eps_low=a.epsilon, eps_high=eps_high)
-                elif use_is:
-                    form = dict(rollout_logp=ro_all[r0:r1].contiguous(), cap=a.rollout_is_cap, level=a.rollout_is_level)
-                res = ops.grpo_loss_ex(lp.view(n, C), adv_d[r0:r1].contiguous(), cmask_d[r0:r1].contiguous(), a.beta, ref_logp=None if no_ref else rl.view(n, C),
-                                       row_scale=row_scale, n_total_rows=N, sel=None if sel_d is None else sel_d[r0:r1].contiguous(), **form)
-                dlogp, kl, rloss, rkl = res[:4]
-                if use_clip:
-                    clip_stats[r0:r1] = res[4]
-                elif use_is:
-                    w_all[r0:r1], is_stats[r0:r1] = res[4], res[5]
-            elif use_clip:
-                dlogp, kl, rloss, rkl, clip_stats[r0:r1] = ops.grpo_loss_clip(lp.view(n, C), old_all[r0:r1].contiguous(), rl.view(n, C), adv_d[r0:r1].contiguous(),
-                                                                              cmask_d[r0:r1].contiguous(), a.beta, a.epsilon, eps_high,
-                                                                              w=None if w_clip is None else w_clip[r0:r1].contiguous(), n_total_rows=N)
+            # one call whatever the options: the form follows from old_logp / rollout_logp, and with a reference, row_scale 0 ("grpo") and no sel it is the
+            # form's own entry point, argument for argument
+            form = {}
+            if use_clip:
+                form = dict(old_logp=old_all[r0:r1].contiguous(), w=None if w_clip is None else w_clip[r0:r1].contiguous(), eps_low=a.epsilon, eps_high=eps_high)
             elif use_is:
-                dlogp, kl, rloss, rkl, w_all[r0:r1], is_stats[r0:r1] = ops.grpo_loss_is(lp.view(n, C), rl.view(n, C), ro_all[r0:r1].contiguous(), adv_d[r0:r1].contiguous(),
-                                                                                      cmask_d[r0:r1].contiguous(), a.beta, a.rollout_is_cap, a.rollout_is_level, n_total_rows=N)
-            else:
-                dlogp, kl, rloss, rkl = ops.grpo_loss(lp.view(n, C), rl.view(n, C), adv_d[r0:r1].contiguous(), cmask_d[r0:r1].contiguous(), a.beta, n_total_rows=N)
+                form = dict(rollout_logp=ro_all[r0:r1].contiguous(), cap=a.rollout_is_cap, level=a.rollout_is_level)
+            res = ops.grpo_loss_ex(lp.view(n, C), adv_d[r0:r1].contiguous(), cmask_d[r0:r1].contiguous(), a.beta, ref_logp=None if no_ref else rl.view(n, C),
+                                   row_scale=row_scale, n_total_rows=N, sel=None if sel_d is None else sel_d[r0:r1].contiguous(), **form)
+            dlogp, kl, rloss, rkl = res[:4]
+            if use_clip:
+                clip_stats[r0:r1] = res[4]
+            elif use_is:
+                w_all[r0:r1], is_stats[r0:r1] = res[4], res[5]
             logp_all[r0:r1] = lp.view(n, C)
             if not no_ref:
                 ref_all[r0:r1], kl_all[r0:r1] = rl.view(n, C), kl

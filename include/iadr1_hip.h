@@ -279,66 +279,62 @@ int iadr1_linear_logprob_fwd(const void* H, const void* W, const long long* targ
                              long long ldh, long long ldw, iadr1_stream_t stream);
 int iadr1_linear_logprob_dlogits(const void* H, const void* W, const long long* targets, const float* lse, const float* g, void* dl, long long ldd,
                                  int M, int V, int K, long long ldh, long long ldw, iadr1_stream_t stream);
-/* n_total_rows: number of sequences the batch mean runs over (>= N when the step is micro-batched) */
-int iadr1_grpo_loss(const float* logp, const float* ref_logp, const float* adv, const int* mask, float beta, int n_total_rows,
+/* The GRPO loss: five entry points, ONE kernel body and ONE host function behind them (csrc/loss.hip).  Over one rank's [N, C] completion block, mask m,
+ * cnt = sum_i m_i, kl_i = exp(d) - d - 1 with d = ref_logp_i - logp_i, the per-token term is  w_i * (-(q_i s_i - beta * kl_i))  and its derivative in logp_i is
+ * g_i = w_i * (beta * (1 - exp(ref_logp_i - logp_i)) - q_i s'_i);  w_i is a constant under differentiation, kl and row_kl stay unweighted.  Three forms differ in
+ * s and w only, and the inputs select the form:
+ *   plain (neither old_logp nor rollout_logp; iadr1_grpo_loss):  s_i = A, s'_i = A, w_i = 1   (REF:...sc_grpo_trainer.py:746,796-798,816; exp(p - sg p) = 1 in value)
+ *   IS    (rollout_logp; iadr1_grpo_loss_is):    s_i = s'_i = A, w_i the truncated importance weight (cap, level, w_out, row_stats [N, 5])
+ *   clip  (old_logp; iadr1_grpo_loss_clip):      s_i = min(r_i A, rc_i A), s'_i = r_i A or 0 where clipped, w_i = w[i] or 1 (eps_low, eps_high, row_stats [N, 4])
+ * iadr1_grpo_loss, _is and _clip demand their form; iadr1_grpo_loss_ex and _sel deduce it from old_logp / rollout_logp and add row_scale and (_sel) q_i = sel_i.
+ *   s = row_scale > 0 ? row_scale : (cnt > 0 ? 1 / cnt : 0)      (the three older calls: row_scale 0)
+ *   row_loss = s * sum_i m_i * term_i,   dlogp_i = m_i * s / n_total_rows * g_i,   row_kl = sum_i m_i kl_i / cnt  whatever row_scale is
+ * n_total_rows: number of sequences the batch mean runs over (>= N when the step is micro-batched).  Log-probs at m_i == 0 (rollout_logp, old_logp) may hold
+ * anything, NaN included: they are never exponentiated.  One block per row, fixed-order block reductions, no float atomics: run-to-run bit-identical.
+ * Bit-equality where a newer call's additions are neutral: _ex with row_scale == 0 is the form's own entry point on every output (reference given or not); _sel with sel
+ * NULL is _ex (same kernels and arguments) and with sel all ones equals it; IS with rollout_logp == logp bitwise and clip with old_logp == logp bitwise (w NULL, or w = an IS
+ * call's w_out) give the four shared outputs of the plain form (of that IS call).
+ * Refused on the host by every entry point, with its own prefix ("grpo_loss_is: ..."): N <= 0, C <= 0, n_total_rows < N; ref_logp NULL with beta != 0 (with beta == 0 it
+ * is legal everywhere: no reference log-prob is read, kl_i = 0, kl (if given) and row_kl are written as 0, and on finite inputs dlogp and row_loss equal those of a call
+ * with any ref_logp); the input the demanded form reads NULL (rollout_logp for _is, old_logp for _clip); row_stats NULL where the form writes it; cap < 1 or not finite,
+ * level not in {0, 1} (IS); eps_low not in [0, 1), eps_high < 0 or not finite (clip); and by _ex / _sel: row_scale negative or not finite, old_logp together with
+ * rollout_logp, w without old_logp. */
+int iadr1_grpo_loss(const float* logp, const float* ref_logp /* may be NULL */, const float* adv, const int* mask, float beta, int n_total_rows,
                     float* dlogp, float* kl, float* row_loss, float* row_kl, int N, int C, iadr1_stream_t stream);
-/* grpo_loss_is: iadr1_grpo_loss with a truncated importance weight per token against the rollout's log-probs (the sampler's and the loss's kernels -- and,
- * with FP8 decode weights, their weights -- differ, so the scored tokens are slightly off-policy).  Over the mask m, with d_i = logp_i - rollout_logp_i:
- *   level 0 (token):    w_i = min(exp(d_i), cap)        level 1 (sequence): w_i = min(exp(sum_i m_i d_i / cnt), cap), one value per row
- *   per-token loss  w_i * (-(A - beta * kl_i)),  row_loss = sum m_i * that / cnt,  dlogp_i = m_i / cnt / n_total_rows * w_i * (-A + beta * (1 - exp(ref_i - logp_i)))
- * w is a constant under differentiation; kl and row_kl stay unweighted.  Both log-probs are temperature-1, unfiltered (iadr1_sample_logp's logp_out against
- * iadr1_logprob_rows): the ratio corrects the engine mismatch, not the sampler's temperature / top-k / top-p filter.  rollout_logp at m_i == 0 is never exponentiated.
- * With rollout_logp == logp bitwise the four shared outputs are bit-equal to iadr1_grpo_loss's.
+/* grpo_loss_is: the truncated importance weight per token against the rollout's log-probs (the sampler's and the loss's kernels -- and, with FP8 decode weights,
+ * their weights -- differ, so the scored tokens are slightly off-policy).  Over the mask m, with d_i = logp_i - rollout_logp_i:
+ *   level 0 (token):    w_i = min(exp(d_i), cap)        level 1 (sequence): w_i = min(exp(sum_i m_i d_i / cnt), cap), one value per row (a mean over cnt whatever row_scale)
+ * Both log-probs are temperature-1, unfiltered (iadr1_sample_logp's logp_out against iadr1_logprob_rows): the ratio corrects the engine mismatch, not the sampler's
+ * temperature / top-k / top-p filter.
  *   w_out (may be NULL): [N, C], 0 where the mask is 0.
- *   row_stats: [N, 5] per-row partials { sum m w, live tokens whose untruncated ratio exceeded cap, sum m |d|, max m |d|, sum m (exp(d) - d - 1) }.
- * One block per row, fixed-order block reductions, no float atomics: run-to-run bit-identical.  Refused on the host: N <= 0, rollout_logp NULL, cap < 1 or not
- * finite, level not in {0, 1}. */
-int iadr1_grpo_loss_is(const float* logp, const float* ref_logp, const float* rollout_logp, const float* adv, const int* mask, float beta, float cap,
+ *   row_stats: [N, 5] per-row partials { sum m w, live tokens whose untruncated ratio exceeded cap, sum m |d|, max m |d|, sum m (exp(d) - d - 1) }. */
+int iadr1_grpo_loss_is(const float* logp, const float* ref_logp /* may be NULL */, const float* rollout_logp, const float* adv, const int* mask, float beta, float cap,
                        int level, int n_total_rows, float* dlogp, float* kl, float* row_loss, float* row_kl, float* w_out, float* row_stats, int N, int C,
                        iadr1_stream_t stream);
 /* grpo_loss_clip: the clipped surrogate of trl's GRPOTrainer (REF:trl/trl/trainer/grpo_trainer.py:1203-1213, loss_type "grpo") for optimizer steps that reuse a
  * rollout (num_iterations > 1; REF:...grpo_trainer.py:741-755).  old_logp: the log-probs of the policy that sampled, scored once per generation (REF:995-1002).
  * Over the mask m, with d_i = logp_i - old_logp_i, r_i = exp(d_i), rc_i = clamp(r_i, 1 - eps_low, 1 + eps_high):
- *   per-token loss  w_i * (-(min(r_i A, rc_i A) - beta * kl_i)),  row_loss = sum m_i * that / cnt,  kl_i as in iadr1_grpo_loss
  *   a token is clipped when r_i < 1 - eps_low and A < 0 (low) or r_i > 1 + eps_high and A > 0 (high), both strict
- *   dlogp_i = m_i / cnt / n_total_rows * w_i * ((clipped ? 0 : -A r_i) + beta * (1 - exp(ref_i - logp_i)))
- * w (may be NULL: 1): [N, C] per-token weights, constant under differentiation -- the w_out of the iadr1_grpo_loss_is call of the step that sampled; kl and
- * row_kl stay unweighted.  old_logp at m_i == 0 may hold anything (NaN included): it is never exponentiated.  With old_logp == logp bitwise the four shared
- * outputs are bit-equal to iadr1_grpo_loss's (w NULL) or to those of the iadr1_grpo_loss_is call whose w_out is passed as w.
- *   row_stats: [N, 4] per-row partials { low-clipped live tokens, high-clipped live tokens, sum m r, max m |d| }.
- * One block per row, fixed-order block reductions, no float atomics: run-to-run bit-identical.  Refused on the host: N <= 0, old_logp or row_stats NULL, eps_low
- * not in [0, 1), eps_high < 0 or not finite, C <= 0, n_total_rows < N. */
-int iadr1_grpo_loss_clip(const float* logp, const float* old_logp, const float* ref_logp, const float* adv, const int* mask, const float* w /* may be NULL */,
+ * w (may be NULL: 1): [N, C] per-token weights -- the w_out of the iadr1_grpo_loss_is call of the step that sampled.
+ *   row_stats: [N, 4] per-row partials { low-clipped live tokens, high-clipped live tokens, sum m r, max m |d| }. */
+int iadr1_grpo_loss_clip(const float* logp, const float* old_logp, const float* ref_logp /* may be NULL */, const float* adv, const int* mask, const float* w /* may be NULL */,
                          float beta, float eps_low, float eps_high, int n_total_rows, float* dlogp, float* kl, float* row_loss, float* row_kl,
                          float* row_stats /* [N,4] */, int N, int C, iadr1_stream_t stream);
-/* grpo_loss_ex: the three calls above behind one entry point, with the two things trl's GRPOTrainer has and they lack: the row normaliser of its `loss_type`
+/* grpo_loss_ex: any of the three forms, with the two things trl's GRPOTrainer has beyond them: the row normaliser of its `loss_type`
  * (REF:trl/trl/trainer/grpo_trainer.py:1212-1219) and a step without a reference model (beta == 0: REF:...grpo_trainer.py:407, 1004-1005, 1193, 1209, 1224).
- * Which form runs follows from the optional inputs: old_logp -> the clipped surrogate of iadr1_grpo_loss_clip (REF:1203-1210; w as there), rollout_logp -> the
- * truncated importance weight of iadr1_grpo_loss_is (cap, level, w_out), neither -> iadr1_grpo_loss (REF:1192-1202 with exp(p - sg p) = 1).  t_i is that form's
- * per-token term, g_i its derivative and w_i its weight (1 where the form has none), all exactly as in those calls.  Over the mask m, cnt = sum_i m_i:
- *   s = row_scale > 0 ? row_scale : (cnt > 0 ? 1 / cnt : 0)
- *   row_loss = s * sum_i m_i w_i t_i,   dlogp_i = m_i * s / n_total_rows * w_i * g_i,   row_kl = sum_i m_i kl_i / cnt  whatever row_scale is
- * so that mean(row_loss) over the N = n_total_rows rows of a step is trl's loss for
+ * mean(row_loss) over the N = n_total_rows rows of a step is trl's loss for
  *   row_scale 0 ("grpo", REF:1213: every row a mean over its own live tokens),   row_scale N / max(live tokens of the batch, 1) ("bnpo", REF:1215),
  *   row_scale 1 / max_completion_length ("dr_grpo", REF:1217).
- * The sequence-level importance ratio keeps its row mean over cnt.  ref_logp NULL (needs beta == 0): no reference log-prob is read, kl_i = 0, kl (if given)
- * and row_kl are written as 0 and the gradient is the advantage term alone -- on finite inputs dlogp and row_loss equal those of a call with any ref_logp at
- * beta == 0.  With ref_logp given and row_scale == 0 every output is bit-equal to the matching call above.  kl, w_out may be NULL; row_stats: [N, 5] (IS form),
- * [N, 4] (clipped form), unused (may be NULL) otherwise.  One block per row, fixed-order block reductions, no float atomics: run-to-run bit-identical.
- * Refused on the host: ref_logp NULL with beta != 0; row_scale negative or not finite; old_logp together with rollout_logp; w without old_logp; row_stats NULL
- * where the form writes it; cap / level (IS form) and eps_low / eps_high (clipped form) as in those calls; N <= 0, C <= 0, n_total_rows < N. */
+ * kl, w_out may be NULL; row_stats: [N, 5] (IS form), [N, 4] (clipped form), unused (may be NULL) otherwise. */
 int iadr1_grpo_loss_ex(const float* logp, const float* ref_logp /* may be NULL */, const float* old_logp /* may be NULL */, const float* rollout_logp /* may be NULL */,
                        const float* w /* may be NULL */, const float* adv, const int* mask, float beta, float cap, int level, float eps_low, float eps_high,
                        float row_scale, int n_total_rows, float* dlogp, float* kl /* may be NULL */, float* row_loss, float* row_kl, float* w_out /* may be NULL */,
                        float* row_stats, int N, int C, iadr1_stream_t stream);
 /* grpo_loss_sel: iadr1_grpo_loss_ex with a per-token selector on the ADVANTAGE term -- trl's top_entropy_quantile, which trains the policy term on the
  * highest-entropy share of the completion tokens only (trl's GRPOTrainer get_high_entropy_mask; the mask multiplies per_token_loss1 / per_token_loss2 there and
- * the KL term is added behind it).  sel: [N, C] int32 of 0 / 1 in the layout of mask.  With q_i = sel_i and s_i = A (plain and IS forms) or min(r_i A, rc_i A)
- * (clipped form):  t_i = -(q_i s_i - beta kl_i),  and g_i is iadr1_grpo_loss_ex's with its advantage part multiplied by q_i.  Everything else is that call's and
- * stays over the LIVE tokens (mask): the KL part of t_i and g_i, kl, row_kl, the row normaliser (cnt, row_scale), the sequence-level importance ratio, w_out and
- * every column of row_stats (the clip counts included).  The gate is a select in front of the advantage operand, never a product by 1.0: with sel all ones
- * every output is bit-equal to iadr1_grpo_loss_ex's.  sel == NULL: iadr1_grpo_loss_ex's own kernels and arguments.  Refusals: iadr1_grpo_loss_ex's, with the
- * prefix "grpo_loss_sel:". */
+ * the KL term is added behind it).  sel: [N, C] int32 of 0 / 1 in the layout of mask, q_i = sel_i.  Everything else stays over the LIVE tokens (mask): the KL part of
+ * the term and of g_i, kl, row_kl, the row normaliser (cnt, row_scale), the sequence-level importance ratio, w_out and every column of row_stats (the clip counts
+ * included).  The gate is a select in front of the advantage operand, never a product by 1.0. */
 int iadr1_grpo_loss_sel(const float* logp, const float* ref_logp /* may be NULL */, const float* old_logp /* may be NULL */, const float* rollout_logp /* may be NULL */,
                         const float* w /* may be NULL */, const float* adv, const int* mask, float beta, float cap, int level, float eps_low, float eps_high,
                         float row_scale, int n_total_rows, float* dlogp, float* kl /* may be NULL */, float* row_loss, float* row_kl, float* w_out /* may be NULL */,

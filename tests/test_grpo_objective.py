@@ -63,6 +63,22 @@ def test_bad_arguments_are_refused_on_the_host(kw, word):
     assert rc < 0 and "grpo_loss_ex" in msg and word in msg, (rc, msg)
 
 
+@pytest.mark.parametrize("name", ["grpo_loss", "grpo_loss_is", "grpo_loss_clip"])
+def test_the_older_entry_points_refuse_a_null_reference_with_a_kl_term(name):
+    """ref_logp NULL with beta != 0 on otherwise valid host buffers: refused before anything is launched, with iadr1_grpo_loss_ex's rule and the entry point's prefix."""
+    L = hip.lib()
+    buf = (ctypes.c_float * 64)()
+    p = ctypes.addressof(buf)
+    if name == "grpo_loss":
+        rc = L.iadr1_grpo_loss(p, None, p, p, BETA, 2, p, p, p, p, 2, 4, None)
+    elif name == "grpo_loss_is":
+        rc = L.iadr1_grpo_loss_is(p, None, p, p, p, BETA, CAP, 0, 2, p, p, p, p, p, p, 2, 4, None)
+    else:
+        rc = L.iadr1_grpo_loss_clip(p, p, None, p, p, None, BETA, EL, EH, 2, p, p, p, p, p, 2, 4, None)
+    msg = L.iadr1_last_error().decode()
+    assert rc < 0 and msg.startswith(name + ":") and "ref_logp" in msg, (rc, msg)
+
+
 def _grpo_ad():
     spec = importlib.util.spec_from_file_location("grpo_ad_objective_flags", os.path.join(ROOT, "train", "stage_rl", "grpo_ad.py"))
     mod = importlib.util.module_from_spec(spec)
@@ -351,6 +367,26 @@ def test_null_reference_equals_a_given_one_at_beta_zero(N, C):
                 assert bool(torch.isfinite(given[0]).all()) and torch.equal(given[0], null[0]) and torch.equal(given[2], null[2]), what
                 assert bool((null[1] == 0).all()) and bool((null[3] == 0).all()), what
                 assert all(torch.equal(a, b) for a, b in zip(given[4:], null[4:])), what        # the weights and the partials do not involve the reference
+
+
+@pytest.mark.gpu
+def test_the_older_entry_points_run_without_a_reference_at_beta_zero():
+    """N = 3, C = 300 (the second trip of the 256-wide loops), row 0 without a live token, row 1 partly live, row 2 full: iadr1_grpo_loss / _is / _clip with
+    ref_logp NULL and beta 0 give every output torch.equal to grpo_loss_ex(ref_logp=None) of the same form, no NaN, and zeros on the empty row."""
+    t = kernel_inputs(3, 300, "mixed", seed=77, lens=[0, 131, 300])
+    p, adv, mask = t["p"], t["adv"], t["mask"]
+    for form in FORMS:
+        if form == "plain":
+            old = ops.grpo_loss(p, None, adv, mask, 0.0)
+        elif form.startswith("is_"):
+            old = ops.grpo_loss_is(p, None, t["q"], adv, mask, 0.0, CAP, form[3:])
+        else:
+            old = ops.grpo_loss_clip(p, t["old"], None, adv, mask, 0.0, EL, EH, w=t["w"] if form == "clip_w" else None)
+        new = ops.grpo_loss_ex(p, adv, mask, 0.0, ref_logp=None, **form_args(t, form))
+        assert len(old) == len(new)
+        for k, (a, b) in enumerate(zip(old, new)):
+            assert torch.equal(a, b) and not bool(torch.isnan(a).any()), (form, k)
+            assert bool((a[0] == 0).all()), (form, k, a[0])
 
 
 @pytest.mark.gpu

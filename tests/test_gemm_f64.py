@@ -1,6 +1,6 @@
 """The training GEMMs and the fused lm_head of csrc/gemm.hip against float64: iadr1_gemm_nt_bf16 (both kernels, out_mode 0 / 1 / 2, bias, GELU), iadr1_gemm_nt_splitk_acc_bf16,
 iadr1_gemm_tn_acc_bf16 (un-split and split), iadr1_gemm_swiglu_bf16 (GU stored and NULL), iadr1_gemm_swiglu_rows_bf16, iadr1_linear_logprob_fwd and iadr1_linear_logprob_dlogits.
-csrc/skinny.hip (the decode GEMMs) is not covered here.  The structure and the helpers (Guard, frac, bfr, same_bits, ...) are those of test_tokenwise_f64.py.
+csrc/skinny.hip (the decode GEMMs and their packers) has its own file, test_skinny_f64.py.  The structure and the helpers (Guard, frac, bfr, same_bits, ...) are those of test_tokenwise_f64.py.
 
 THE BOUND.  Every output element is held to   |got - ref64| <= 2^-8 c |ref64| + 2^-24 (f0 E + fn n E) + 1e-30   (no element is exempt).  ref64 is the operation in float64 on the
 same bf16-rounded inputs with NO intermediate rounding, E the same formula with the absolute value of every term, E = sum_k |a| |b| + |bias| + |C0|, and n = K.

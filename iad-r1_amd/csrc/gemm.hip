@@ -54,12 +54,30 @@ struct GemmArgs {
     // consecutive rows rb_stride rows apart (the rows a chunk of decode steps produced in a sequence-major arena)
     int rb_shift;
     long long rb_stride;
+    // OUT_LSE / OUT_DLOGITS at a temperature (iadr1_linear_logprob_fwd_t / _dlogits_t): both epilogues work on y = x * inv_t, inv_t = 1 / T formed once on the host
+    float inv_t = 1.f;
 };
 
 enum { OUT_BF16 = 0, OUT_F32 = 1, OUT_F32_ACC = 2, OUT_SWIGLU = 3, OUT_LSE = 4, OUT_DLOGITS = 5, OUT_SWIGLU_ROWS = 6 };
 
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void gbl_void;
+
+// y = x * inv_t as ONE fp32 multiply per accumulator element, in place, before an epilogue reads it; the empty asm keeps -ffp-contract from fusing the product
+// into the subtraction that follows it.  Registers only: no pointer, LDS or store.  inv_t == 1: the same bits.
+template <int MI>
+__device__ __forceinline__ void scale_acc(f32x4_t (&acc)[MI][4], float inv_t) {
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float y = acc[i][j][e] * inv_t;
+                asm volatile("" : "+v"(y));
+                acc[i][j][e] = y;
+            }
+}
 
 __device__ __forceinline__ void glds16(const void* g, char* lds_wave_base) {
     // LDS destination = wave-uniform base + lane*16 (hardware rule); source address is per lane.
@@ -596,6 +614,7 @@ __global__ __launch_bounds__(NT2, 2) void gemm_nt_256(GemmArgs p) {
     } else if constexpr (OUT == OUT_LSE) {
         // linear_logprob forward: per row and 64-column wave slice the pair (max, sum exp(x - max)) and the logit at the row's target column; the
         // logits themselves are never stored.  Lane (lm, lq) holds columns j*16 + lq*4 + e of rows i*16 + lm: in-lane over (j, e), then over lq.
+        scale_acc(acc, p.inv_t);    // from here on acc holds y = x / T (REF:trl/trl/trainer/grpo_trainer.py:818-821)
         const int cbase = n0 + wn * 64;
         const bool full = cbase + 64 <= p.N;
 #pragma unroll
@@ -637,11 +656,13 @@ __global__ __launch_bounds__(NT2, 2) void gemm_nt_256(GemmArgs p) {
         __syncthreads();  // every wave is done with the operand buffers
         bf16_t* slab = (bf16_t*)smem + (size_t)w * 128 * EP_LD;
         if constexpr (OUT == OUT_DLOGITS) {
-            // linear_logprob backward: the recomputed logits leave as dlogits = g * (onehot(target) - exp(x - lse)) in bf16 (iadr1_dlogits_rows's arithmetic)
+            // linear_logprob backward: the recomputed logits leave as dlogits = g * (onehot(target) - exp(x - lse)) in bf16 (iadr1_dlogits_rows's arithmetic);
+            // at a temperature on y = x / T, with the chain rule's 1 / T on g
+            scale_acc(acc, p.inv_t);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const int row = min(m0 + wm * 128 + i * 16 + lm, p.M - 1);
-                const float rl = p.lse[row], rg = p.g[row];
+                const float rl = p.lse[row], rg = p.g[row] * p.inv_t;
                 const long long tg = p.targets[row];
                 const int d = (tg >= 0 && tg < p.N) ? (int)tg - (n0 + wn * 64) - lq * 4 : -1;
 #pragma unroll
@@ -938,33 +959,65 @@ static int linear_logprob_args(const char* what, const void* H, const void* W, i
     return 0;
 }
 
-extern "C" int iadr1_linear_logprob_fwd(const void* H, const void* W, const long long* targets, float* logp, float* lse, void* workspace, int M, int V, int K,
-                                        long long ldh, long long ldw, hipStream_t stream) {
-    if (int rc = linear_logprob_args("linear_logprob_fwd", H, W, M, V, K, ldh, ldw)) return rc;
-    IADR1_REQUIRE(targets && logp && workspace && (((uintptr_t)workspace) & 7) == 0, "linear_logprob_fwd: targets, logp and an 8-byte aligned workspace are required");
+// The two forms of each entry point are one function: `what` is the entry point's name (the prefix of its refusals), temperature 1 the plain form's.
+static int linear_logprob_temperature(const char* what, float temperature) {
+    IADR1_REQUIRE(temperature > 0.f && temperature <= 3.402823466e38f, "%s: temperature must be finite and > 0 (got %g)", what, (double)temperature);
+    return 0;
+}
+
+static int linear_logprob_fwd(const char* what, const char* what_combine, const void* H, const void* W, const long long* targets, float* logp, float* lse, void* workspace, int M, int V, int K,
+                              long long ldh, long long ldw, float temperature, hipStream_t stream) {
+    if (int rc = linear_logprob_temperature(what, temperature)) return rc;
+    if (int rc = linear_logprob_args(what, H, W, M, V, K, ldh, ldw)) return rc;
+    IADR1_REQUIRE(targets && logp && workspace && (((uintptr_t)workspace) & 7) == 0, "%s: targets, logp and an 8-byte aligned workspace are required", what);
     constexpr int band_rows = 4;      // tile rows per rasterisation band: 1 / 2 / 4 / 8 measured within 4 % on the hot shapes, 4 best (profiles/r05_gemm_band.txt)
     const int tiles_n = (V + T2 - 1) / T2, nparts = tiles_n * 4;
     float* part = (float*)workspace;
     float* tgt_logit = part + (long long)M * nparts * 2;
     GemmArgs p{(const bf16_t*)H, (const bf16_t*)W, nullptr, nullptr, zeros_ptr(), M, V, K, ldh, ldw, 0, 0, band_rows, nullptr, 0, targets, part, tgt_logit, nullptr, nullptr, nparts};
+    p.inv_t = 1.0f / temperature;
     static const bool attr_done = [] { (void)hipFuncSetAttribute((const void*)gemm_nt_256<OUT_LSE>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM2_BYTES); return true; }();
     (void)attr_done;
     hipLaunchKernelGGL(gemm_nt_256<OUT_LSE>, dim3(((M + T2 - 1) / T2) * tiles_n), dim3(NT2), SMEM2_BYTES, stream, p);
-    if (int rc = iadr1_check_launch("linear_logprob_fwd")) return rc;
+    if (int rc = iadr1_check_launch(what)) return rc;
     hipLaunchKernelGGL(lse_combine_kernel, dim3((M + 3) / 4), dim3(256), 0, stream, part, tgt_logit, targets, logp, lse, M, V, nparts);
-    return iadr1_check_launch("linear_logprob_fwd (combine)");
+    return iadr1_check_launch(what_combine);
+}
+
+static int linear_logprob_dlogits(const char* what, const void* H, const void* W, const long long* targets, const float* lse, const float* g, void* dl, long long ldd, int M,
+                                  int V, int K, long long ldh, long long ldw, float temperature, hipStream_t stream) {
+    if (int rc = linear_logprob_temperature(what, temperature)) return rc;
+    if (int rc = linear_logprob_args(what, H, W, M, V, K, ldh, ldw)) return rc;
+    IADR1_REQUIRE(targets && lse && g && dl, "%s: targets, lse, g and dl are required", what);
+    constexpr int band_rows = 4;      // tile rows per rasterisation band: 1 / 2 / 4 / 8 measured within 4 % on the hot shapes, 4 best (profiles/r05_gemm_band.txt)
+    GemmArgs p{(const bf16_t*)H, (const bf16_t*)W, dl, nullptr, zeros_ptr(), M, V, K, ldh, ldw, ldd, 0, band_rows, nullptr, 0, targets, nullptr, nullptr, lse, g, 0};
+    p.inv_t = 1.0f / temperature;
+    static const bool attr_done = [] { (void)hipFuncSetAttribute((const void*)gemm_nt_256<OUT_DLOGITS>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM2_BYTES); return true; }();
+    (void)attr_done;
+    hipLaunchKernelGGL(gemm_nt_256<OUT_DLOGITS>, dim3(((M + T2 - 1) / T2) * ((V + T2 - 1) / T2)), dim3(NT2), SMEM2_BYTES, stream, p);
+    return iadr1_check_launch(what);
+}
+
+extern "C" int iadr1_linear_logprob_fwd(const void* H, const void* W, const long long* targets, float* logp, float* lse, void* workspace, int M, int V, int K,
+                                        long long ldh, long long ldw, hipStream_t stream) {
+    return linear_logprob_fwd("linear_logprob_fwd", "linear_logprob_fwd (combine)", H, W, targets, logp, lse, workspace, M, V, K, ldh, ldw, 1.f, stream);
 }
 
 extern "C" int iadr1_linear_logprob_dlogits(const void* H, const void* W, const long long* targets, const float* lse, const float* g, void* dl, long long ldd, int M, int V,
                                             int K, long long ldh, long long ldw, hipStream_t stream) {
-    if (int rc = linear_logprob_args("linear_logprob_dlogits", H, W, M, V, K, ldh, ldw)) return rc;
-    IADR1_REQUIRE(targets && lse && g && dl, "linear_logprob_dlogits: targets, lse, g and dl are required");
-    constexpr int band_rows = 4;      // tile rows per rasterisation band: 1 / 2 / 4 / 8 measured within 4 % on the hot shapes, 4 best (profiles/r05_gemm_band.txt)
-    GemmArgs p{(const bf16_t*)H, (const bf16_t*)W, dl, nullptr, zeros_ptr(), M, V, K, ldh, ldw, ldd, 0, band_rows, nullptr, 0, targets, nullptr, nullptr, lse, g, 0};
-    static const bool attr_done = [] { (void)hipFuncSetAttribute((const void*)gemm_nt_256<OUT_DLOGITS>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM2_BYTES); return true; }();
-    (void)attr_done;
-    hipLaunchKernelGGL(gemm_nt_256<OUT_DLOGITS>, dim3(((M + T2 - 1) / T2) * ((V + T2 - 1) / T2)), dim3(NT2), SMEM2_BYTES, stream, p);
-    return iadr1_check_launch("linear_logprob_dlogits");
+    return linear_logprob_dlogits("linear_logprob_dlogits", H, W, targets, lse, g, dl, ldd, M, V, K, ldh, ldw, 1.f, stream);
+}
+
+// The same pair on y = x / temperature (REF:trl/trl/trainer/grpo_trainer.py:818-821: trl scores the policy, the old policy and the reference on logits / temperature):
+// lse = logsumexp(y), logp = y[target] - lse, dl = (g / T) * (onehot - exp(y - lse)).  The same two kernels; temperature 1 gives the plain pair's bits.
+extern "C" int iadr1_linear_logprob_fwd_t(const void* H, const void* W, const long long* targets, float* logp, float* lse, void* workspace, int M, int V, int K,
+                                          long long ldh, long long ldw, float temperature, hipStream_t stream) {
+    return linear_logprob_fwd("linear_logprob_fwd_t", "linear_logprob_fwd_t (combine)", H, W, targets, logp, lse, workspace, M, V, K, ldh, ldw, temperature, stream);
+}
+
+extern "C" int iadr1_linear_logprob_dlogits_t(const void* H, const void* W, const long long* targets, const float* lse, const float* g, void* dl, long long ldd, int M,
+                                              int V, int K, long long ldh, long long ldw, float temperature, hipStream_t stream) {
+    return linear_logprob_dlogits("linear_logprob_dlogits_t", H, W, targets, lse, g, dl, ldd, M, V, K, ldh, ldw, temperature, stream);
 }
 
 // gate|up projection with the SwiGLU fused into the epilogue of gemm_nt_256 (training / prefill shapes): GU[M, 2I] = A . W^T (stored when GU != null:

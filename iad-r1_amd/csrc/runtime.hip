@@ -83,6 +83,8 @@ extern "C" int iadr1_stream_destroy(void* stream) {
 }
 
 extern "C" const char* iadr1_last_error(void) { return g_err; }
+// 118: iadr1_linear_logprob_fwd_t / iadr1_linear_logprob_dlogits_t (the fused lm_head pair on logits / temperature) and iadr1_sample_ent_t (the rollout's log-prob and
+//      entropy at a temperature of their own); nothing else changed
 // 117: iadr1_sample_ent / iadr1_sample_ent_workspace_bytes (the entropy of the raw row's softmax beside the log-prob of the pick) and iadr1_grpo_loss_sel (a per-token
 //      selector on the advantage term: top_entropy_quantile); nothing else changed
 // 116: iadr1_sample_guided / iadr1_sample_guided_workspace_bytes (regex-guided decoding: a per-row automaton state, an allowed-token bitmap and a transition table per
@@ -96,5 +98,5 @@ extern "C" const char* iadr1_last_error(void) { return g_err; }
 // 106: round 5 -- CU-masked streams, decode CU count, iadr1_attn_fwd_chunk, iadr1_wait_counter (co-scheduled rollout / teacher-forced forward); ordered two-stage
 //      gradient reductions: workspace arguments on iadr1_rmsnorm_bwd / iadr1_layernorm_bwd / iadr1_colsum_acc, iadr1_rows_scatter_acc replaces iadr1_embed_bwd
 // 104: round 4 -- iadr1_decode_advance gained the all_done / rotary-table arguments, the FP8-MFMA pair (iadr1_quant_rows_fp8, iadr1_gemm_nt_fp8) is gone
-extern "C" int iadr1_version(void) { return 117; }
+extern "C" int iadr1_version(void) { return 118; }
 

@@ -12,12 +12,15 @@
 //   stage 2: grid (B): the NCHUNK*K survivors -> exact global top-K (same routine) -> rank sort -> softmax,
 //            top-p cut, inverse-CDF draw.
 //
-// ONE body per stage, stage1<LP, EX, GD, EN> and stage2<LP, EX, GD, EN>, behind all five entry points; a flag that is off compiles its code out:
+// ONE body per stage, stage1<LP, EX, GD, EN> and stage2<LP, EX, GD, EN>, behind all six entry points; a flag that is off compiles its code out:
 //   LP  the log-prob of the pick + whole-vocabulary sampling for top_k <= 0     iadr1_sample_topk_topp: sample_stage1/2 <0, 0, 0>; iadr1_sample_logp: sample_logp_stage1/2 <1, 0, 0>
 //   EX  a repetition penalty in front of the filter and a min_p cut behind it   iadr1_sample_ex: sample_ex_stage1/2 <1, 1, 0>
 //   GD  a per-row automaton's mask in front of everything the filter does       iadr1_sample_guided: sample_guided_stage1/2 <1, 1, 1>; without a guide sample_ex's pair
 //   EN  the entropy of the raw row's softmax beside the log-prob of the pick     iadr1_sample_ent: sample_ent_stage1/2 <1, 1, 0, 1>, with a guide sample_ent_guided_stage1/2 <1, 1, 1, 1>; without ent_out sample_guided's launch
+// iadr1_sample_ent_t is iadr1_sample_ent's launch with LogpArgs.inv_tl = 1 / logp_temperature: the log-prob and the entropy at that temperature, no flag of its own.
 // The ids of two entry points are bit-equal wherever the newer one's additions are neutral, because they are this code.  The host side is one function too.
+#include <string.h>
+
 #include "common.h"
 
 namespace {
@@ -221,7 +224,7 @@ __device__ __forceinline__ int topk_topp_pick(const SampleArgs& p, int row, cons
 
 // ---- LP: whole-vocabulary sampling (top_k <= 0) + the log-prob of the pick ----------------------------------------------------------------------
 // Both need the softmax normaliser of the WHOLE row.  Stage 1 holds its slice in registers anyway: it also reduces it to
-//   (m1, s1) = (max x, sum exp(x - m1))                 temperature 1, nothing filtered or suppressed: what the loss scores (iadr1_logprob_rows)
+//   (m1, s1) = (max x, sum exp((x - m1) * inv_tl))      nothing filtered or suppressed: what the loss scores (inv_tl = 1: iadr1_logprob_rows; iadr1_sample_ent_t: 1 / T)
 //   (mT, sT) = (max x, sum exp((x - mT) / T))           suppressed token excluded; only for top_k <= 0
 // four floats per (row, chunk) behind the candidate lists.  Stage 2 merges the NCHUNK partials with one wave (fixed shuffle trees, no atomics on floats).
 // Whole vocabulary: an inclusive scan of the chunk masses in chunk order finds the chunk that holds u * total, that ONE slice is read again and an
@@ -234,6 +237,7 @@ struct LogpArgs {
     float* logp;        // optional [B, ld] log-probs, column = the step value
     long long ld;
     int cols;
+    float inv_tl;       // 1 / the temperature the log-prob (and EN's entropy) is taken at: softmax(x * inv_tl).  1 everywhere but iadr1_sample_ent_t
 };
 
 __device__ __forceinline__ bool whole_vocab(const SampleArgs& p) { return p.top_k <= 0 && p.temperature > 0.f; }
@@ -280,10 +284,11 @@ __device__ __forceinline__ void guide_advance(const GuideArgs& g, int row, int s
 }
 
 // ---- EN: the entropy of the distribution the log-prob is taken under ---------------------------------------------------------------------------------------------------
-// H = -sum p ln p with p = softmax(x) over the RAW row at temperature 1: nothing suppressed, masked, penalised or filtered -- (m1, s1)'s distribution.  Stage 1 adds
-//   u1 = sum e_i (x_i - m1),  e_i = exp(x_i - m1)       (x_i = -inf skipped: 0 * -inf; every term <= 0)
-// as a fifth partial per (row, chunk), BEHIND the [B][NCHUNK][4] block.  Stage 2, with a_c = exp(m1_c - M1) (0 for an all--inf chunk):
-//   S = sum s1_c a_c,   U = sum (u1_c + (m1_c - M1) s1_c) a_c,   H = ln S - U / S
+// H = -sum p ln p with p = softmax(x * inv_tl) over the RAW row (inv_tl = 1 but for iadr1_sample_ent_t): nothing suppressed, masked, penalised or filtered -- (m1, s1)'s
+// distribution.  Stage 1 adds
+//   u1 = sum e_i d_i,  d_i = (x_i - m1) * inv_tl,  e_i = exp(d_i)       (x_i = -inf skipped: 0 * -inf; every term <= 0)
+// as a fifth partial per (row, chunk), BEHIND the [B][NCHUNK][4] block.  Stage 2, with d_c = (m1_c - M1) * inv_tl and a_c = exp(d_c) (0 for an all--inf chunk):
+//   S = sum s1_c a_c,   U = sum (u1_c + d_c s1_c) a_c,   H = ln S - U / S
 // ln S >= 0 (the chunk that holds M1 has s1 >= 1) and U <= 0: two non-negative numbers, no cancellation.  Fixed trees, no float atomics.
 struct EntArgs {
     float* part;        // scratch [B][NCHUNK]: u1
@@ -335,8 +340,8 @@ __device__ __forceinline__ void stage1(const SampleArgs& p, const LogpArgs& q, c
         float s1 = 0.f, sT = 0.f;
         if (m1 > -INFINITY) {
 #pragma unroll
-            for (int i = 0; i < ITEMS; ++i) s1 += expf(val[i] - m1);      // (padding and the suppressed slot hold -inf: they add 0)
-            if (xs > -INFINITY) s1 += expf(xs - m1);
+            for (int i = 0; i < ITEMS; ++i) s1 += expf((val[i] - m1) * q.inv_tl);      // (padding and the suppressed slot hold -inf: they add 0)
+            if (xs > -INFINITY) s1 += expf((xs - m1) * q.inv_tl);
         }
         float u1 = 0.f;
         if constexpr (EN) {
@@ -344,10 +349,10 @@ __device__ __forceinline__ void stage1(const SampleArgs& p, const LogpArgs& q, c
             if (m1 > -INFINITY) {
 #pragma unroll
                 for (int i = 0; i < ITEMS; ++i) {
-                    const float d = val[i] - m1;
+                    const float d = (val[i] - m1) * q.inv_tl;
                     if (val[i] > -INFINITY) u1 += expf(d) * d;
                 }
-                if (xs > -INFINITY) u1 += expf(xs - m1) * (xs - m1);
+                if (xs > -INFINITY) { const float d = (xs - m1) * q.inv_tl; u1 += expf(d) * d; }
             }
         }
         if constexpr (GD) {
@@ -402,9 +407,9 @@ __device__ __forceinline__ void stage1(const SampleArgs& p, const LogpArgs& q, c
 
 template <bool LP, bool EX, bool GD, bool EN = false>
 __device__ __forceinline__ void commit_pick(const SampleArgs& p, const ExArgs& e, const GuideArgs& gd, int row, int st, int pick, float* lp, const float* raw, float lse,
-                                            float* hp = nullptr, float H = 0.f) {
+                                            float inv_tl, float* hp = nullptr, float H = 0.f) {
     p.out[row] = pick;
-    if constexpr (LP) { if (lp) *lp = *raw - lse; }
+    if constexpr (LP) { if (lp) *lp = *raw * inv_tl - lse; }
     if constexpr (EN) { if (hp) *hp = H; }
     if constexpr (EX) mark_pick(e, row, pick);
     if constexpr (GD) guide_advance(gd, row, st, pick);
@@ -425,7 +430,7 @@ __device__ __forceinline__ void stage2(const SampleArgs& p, const LogpArgs& q, c
     const float* x = p.logits + (long long)row * p.ld;     // read with LP only: the log-prob's raw logit and the whole-vocabulary draw
     const uint32_t step = read_step(p);     // read once, at entry: the Philox counter of the whole-vocabulary draw and the log-prob column
     float* lp = (LP && q.logp != nullptr && step < (uint32_t)q.cols) ? q.logp + (long long)row * q.ld + step : nullptr;
-    float lse = 0.f;    // the raw row's log-sum-exp at temperature 1 (LP)
+    float lse = 0.f;    // the raw row's log-sum-exp at the log-prob temperature, 1 / q.inv_tl (LP)
     float* hp = nullptr;    // where the row's entropy goes (EN): logp's column rule
     float H = 0.f;
     if constexpr (EN) { if (en.ent != nullptr && step < (uint32_t)en.cols) hp = en.ent + (long long)row * en.ld + step; }
@@ -441,11 +446,12 @@ __device__ __forceinline__ void stage2(const SampleArgs& p, const LogpArgs& q, c
         const float* pr = q.part + ((long long)row * NCHUNK + (have ? lane : 0)) * 4;
         const float m1 = have ? pr[0] : -INFINITY, s1 = have ? pr[1] : 0.f;
         const float M1 = wave_max(m1);
-        const float S = wave_sum(m1 > -INFINITY ? s1 * expf(m1 - M1) : 0.f);
-        lse = M1 + logf(S);
+        const float dm = (m1 - M1) * q.inv_tl;      // (NaN for an all--inf chunk or row: every use sits behind m1 > -inf)
+        const float S = wave_sum(m1 > -INFINITY ? s1 * expf(dm) : 0.f);
+        lse = M1 * q.inv_tl + logf(S);
         if constexpr (EN) {
             const float u1 = have ? en.part[(long long)row * NCHUNK + lane] : 0.f;
-            const float U = wave_sum(m1 > -INFINITY ? (u1 + (m1 - M1) * s1) * expf(m1 - M1) : 0.f);
+            const float U = wave_sum(m1 > -INFINITY ? (u1 + dm * s1) * expf(dm) : 0.f);
             H = S > 0.f ? logf(S) - U / S : 0.f;    // (S == 0: a row of -inf only has no distribution)
         }
         if (whole_vocab(p)) {
@@ -526,7 +532,7 @@ __device__ __forceinline__ void stage2(const SampleArgs& p, const LogpArgs& q, c
             __syncthreads();
             if (t == 0) {
                 const int pick = sh_i[0] != 0x7fffffff ? sh_i[0] : max(sh_i[1], 0);
-                commit_pick<LP, EX, GD, EN>(p, e, gd, row, st, pick, lp, &x[pick], lse, hp, H);
+                commit_pick<LP, EX, GD, EN>(p, e, gd, row, st, pick, lp, &x[pick], lse, q.inv_tl, hp, H);
             }
             return;
         }
@@ -544,7 +550,7 @@ __device__ __forceinline__ void stage2(const SampleArgs& p, const LogpArgs& q, c
     if (p.temperature <= 0.f) {
         if (t == 0) {
             const int pick = n > 0 ? cidx[0] : 0;
-            commit_pick<LP, EX, GD, EN>(p, e, gd, row, st, pick, lp, &x[pick], lse, hp, H);
+            commit_pick<LP, EX, GD, EN>(p, e, gd, row, st, pick, lp, &x[pick], lse, q.inv_tl, hp, H);
         }
         return;
     }
@@ -560,7 +566,7 @@ __device__ __forceinline__ void stage2(const SampleArgs& p, const LogpArgs& q, c
     __syncthreads();
     if (t == 0) {
         const int pick = topk_topp_pick(p, row, sval, cval, n, EX ? e.min_p : 0.f);
-        commit_pick<LP, EX, GD, EN>(p, e, gd, row, st, sidx[pick], lp, &sraw[pick], lse, hp, H);
+        commit_pick<LP, EX, GD, EN>(p, e, gd, row, st, sidx[pick], lp, &sraw[pick], lse, q.inv_tl, hp, H);
     }
 }
 
@@ -600,13 +606,14 @@ void launch_pair(void (*s1)(A...), void (*s2)(A...), int B, hipStream_t stream, 
     hipLaunchKernelGGL(s2, dim3(B), dim3(NT), 0, stream, a...);
 }
 
-// The five entry points: the checks, the workspace carve-up, the argument structs and the launch, once.  `name` is the entry point's ("sample_ex": the prefix of
+// The six entry points: the checks, the workspace carve-up, the argument structs and the launch, once.  `name` is the entry point's ("sample_ex": the prefix of
 // its refusals and the middle of its workspace function's name), `pair` the kernels it launches; under the defaults of what an entry point lacks its checks pass.
 int sample_launch(const char* name, SamplerPair pair, hipStream_t stream, const float* logits, long long ld, long long* out, void* workspace, int B, int V, float temperature,
                   int top_k, float top_p, int suppress_token, unsigned long long seed, unsigned step, const unsigned* step_ptr, const unsigned long long* seed_ptr,
                   float* logp_out = nullptr, long long ld_logp = 0, int logp_cols = 0, float min_p = 0.f, float repetition_penalty = 1.f, unsigned* seen = nullptr,
                   long long ld_seen = 0, int mark_seen = 0, int* state = nullptr, const unsigned* allow = nullptr, long long ld_allow = 0, const short* trans = nullptr,
-                  long long ld_trans = 0, int S = 0, float* ent_out = nullptr, long long ld_ent = 0, int ent_cols = 0) {
+                  long long ld_trans = 0, int S = 0, float* ent_out = nullptr, long long ld_ent = 0, int ent_cols = 0, float logp_temperature = 1.f) {
+    IADR1_REQUIRE(logp_temperature > 0.f && logp_temperature <= 3.402823466e38f, "%s: logp_temperature must be finite and > 0 (got %g)", name, (double)logp_temperature);
     IADR1_REQUIRE(ent_out == nullptr || ent_cols > 0, "%s: ent_out needs ent_cols > 0 (got %d)", name, ent_cols);
     IADR1_REQUIRE(ent_out == nullptr || ld_ent >= ent_cols, "%s: ld_ent=%lld is less than ent_cols = %d", name, ld_ent, ent_cols);
     IADR1_REQUIRE(allow == nullptr || (state != nullptr && trans != nullptr), "%s: allow needs state [B] and trans [S, ld_trans] beside it (got state %s, trans %s)", name,
@@ -625,7 +632,8 @@ int sample_launch(const char* name, SamplerPair pair, hipStream_t stream, const 
     IADR1_REQUIRE(top_p > 0.f && top_p <= 1.f, "%s: top_p must be in (0,1]", name);
     // (the plain pair has no whole-vocabulary path: top_k <= 0 means MAXK candidates there, under any top_p)
     IADR1_REQUIRE(pair == PAIR_PLAIN || top_k > 0 || top_p == 1.f, "%s: top_k <= 0 samples the whole vocabulary and takes top_p = 1 only (got %g): a nucleus over all V tokens is not built", name, (double)top_p);
-    IADR1_REQUIRE(B > 0 && V > 0 && workspace != nullptr, "%s: empty problem or missing workspace (iadr1_%s_workspace_bytes)", name, name);
+    IADR1_REQUIRE(B > 0 && V > 0 && workspace != nullptr, "%s: empty problem or missing workspace (iadr1_%s_workspace_bytes)", name,
+                  strcmp(name, "sample_ent_t") ? name : "sample_ent");     // (iadr1_sample_ent_t takes iadr1_sample_ent's workspace)
     IADR1_REQUIRE(V <= NCHUNK * NT * ITEMS, "%s: V=%d exceeds the built maximum %d", name, V, NCHUNK * NT * ITEMS);
     IADR1_REQUIRE(top_k <= MAXK, "%s: top_k=%d exceeds the built maximum %d", name, top_k, MAXK);
     IADR1_REQUIRE(logp_out == nullptr || (logp_cols > 0 && ld_logp >= logp_cols), "%s: logp_out needs logp_cols > 0 and ld_logp >= logp_cols", name);
@@ -633,7 +641,7 @@ int sample_launch(const char* name, SamplerPair pair, hipStream_t stream, const 
     int* ci = (int*)(cv + (long long)B * NCHUNK * MAXK);
     float* part = (float*)(ci + (long long)B * NCHUNK * MAXK);      // (the plain pair's workspace ends here; it has no LogpArgs)
     SampleArgs p{logits, ld, out, cv, ci, B, V, temperature, top_p, top_k, suppress_token, (uint32_t)seed, (uint32_t)(seed >> 32), step, step_ptr, seed_ptr};
-    LogpArgs q{part, logp_out, ld_logp, logp_cols};
+    LogpArgs q{part, logp_out, ld_logp, logp_cols, 1.0f / logp_temperature};
     ExArgs e{min_p, repetition_penalty, seen, ld_seen, mark_seen != 0};
     GuideArgs g{state, allow, trans, ld_allow, ld_trans, S};
     EntArgs n{part + (long long)B * NCHUNK * 4, ent_out, ld_ent, ent_cols};     // (behind the [B][NCHUNK][4] block: only iadr1_sample_ent's workspace reaches that far)
@@ -696,6 +704,20 @@ extern "C" int iadr1_sample_ent(const float* logits, long long ld, long long* ou
     const SamplerPair pair = ent_out != nullptr ? (allow != nullptr ? PAIR_ENT_GUIDED : PAIR_ENT) : (allow != nullptr ? PAIR_GUIDED : PAIR_EX);
     return sample_launch("sample_ent", pair, stream, logits, ld, out, workspace, B, V, temperature, top_k, top_p, suppress_token, seed, step, step_ptr, seed_ptr, logp_out,
                          ld_logp, logp_cols, min_p, repetition_penalty, seen, ld_seen, mark_seen, state, allow, ld_allow, trans, ld_trans, S, ent_out, ld_ent, ent_cols);
+}
+
+// iadr1_sample_ent with logp_out and ent_out taken under softmax(x / logp_temperature) (REF:trl/trl/trainer/grpo_trainer.py:818-821); which token is picked, the filter,
+// the draw, `seen` and the automaton read what they read there.  The same kernels: stage 1 forms (s1, u1) on (x - m1) * inv_tl, stage 2 merges them on the same scale.
+extern "C" int iadr1_sample_ent_t(const float* logits, long long ld, long long* out, float* logp_out, long long ld_logp, int logp_cols, void* workspace, int B,
+                                  int V, float temperature, int top_k, float top_p, float min_p, float repetition_penalty, unsigned* seen, long long ld_seen,
+                                  int mark_seen, int suppress_token, unsigned long long seed, unsigned step, const unsigned* step_ptr,
+                                  const unsigned long long* seed_ptr, int* state, const unsigned* allow, long long ld_allow, const short* trans,
+                                  long long ld_trans, int S, float* ent_out, long long ld_ent, int ent_cols, float logp_temperature, hipStream_t stream) {
+    // neither output: iadr1_sample_ent's launch (nothing reads the scale)
+    const SamplerPair pair = ent_out != nullptr ? (allow != nullptr ? PAIR_ENT_GUIDED : PAIR_ENT) : (allow != nullptr ? PAIR_GUIDED : PAIR_EX);
+    return sample_launch("sample_ent_t", pair, stream, logits, ld, out, workspace, B, V, temperature, top_k, top_p, suppress_token, seed, step, step_ptr, seed_ptr, logp_out,
+                         ld_logp, logp_cols, min_p, repetition_penalty, seen, ld_seen, mark_seen, state, allow, ld_allow, trans, ld_trans, S, ent_out, ld_ent, ent_cols,
+                         logp_temperature);
 }
 
 extern "C" int iadr1_seen_init(const long long* ids, int S, const int* lengths, int Bp, int G, int V, unsigned* seen, long long ld_seen, hipStream_t stream) {

@@ -560,9 +560,10 @@ def dlogits_rows(logits32, targets, lse, g, out=None):
     return dl
 
 
-def linear_logprob(h, w, targets, logp=None, lse=None, ws=None):
+def linear_logprob(h, w, targets, logp=None, lse=None, ws=None, temperature=1.0):
     """logp[r] = log_softmax(h[r] @ w^T)[targets[r]] (0 for targets < 0) and lse[r], without materialising the [R, V] logits
-    (include/iadr1_hip.h iadr1_linear_logprob_fwd).  ws: uint8 workspace of linear_logprob_ws_bytes(R, V) bytes (allocated when None)."""
+    (include/iadr1_hip.h iadr1_linear_logprob_fwd).  ws: uint8 workspace of linear_logprob_ws_bytes(R, V) bytes (allocated when None).
+    temperature other than 1.0: both of (h[r] @ w^T) / temperature (iadr1_linear_logprob_fwd_t); exactly 1.0 is the plain call."""
     R, K = h.shape
     V, K2 = w.shape
     assert K == K2 and h.dtype == BF16 and w.dtype == BF16 and targets.dtype == torch.int64 and targets.numel() == R
@@ -572,7 +573,10 @@ def linear_logprob(h, w, targets, logp=None, lse=None, ws=None):
     if ws is None:
         ws = torch.empty(need, dtype=torch.uint8, device=h.device)
     assert ws.numel() * ws.element_size() >= need and ws.is_contiguous()
-    hip.call("linear_logprob_fwd", h, w, targets, logp, lse, ws, R, V, K, _ld(h), _ld(w))
+    if temperature == 1.0:
+        hip.call("linear_logprob_fwd", h, w, targets, logp, lse, ws, R, V, K, _ld(h), _ld(w))
+    else:
+        hip.call("linear_logprob_fwd_t", h, w, targets, logp, lse, ws, R, V, K, _ld(h), _ld(w), float(temperature))
     return logp, lse
 
 
@@ -580,12 +584,16 @@ def linear_logprob_ws_bytes(R, V):
     return int(hip.lib().iadr1_linear_logprob_workspace_bytes(R, V))
 
 
-def linear_logprob_dlogits(h, w, targets, lse, g, out=None):
-    """dl[R, V] (bf16) = g[r] * (onehot(targets[r]) - softmax(h[r] @ w^T)) from recomputed logits (iadr1_linear_logprob_dlogits)."""
+def linear_logprob_dlogits(h, w, targets, lse, g, out=None, temperature=1.0):
+    """dl[R, V] (bf16) = g[r] * (onehot(targets[r]) - softmax(h[r] @ w^T)) from recomputed logits (iadr1_linear_logprob_dlogits).  temperature other than 1.0:
+    (g[r] / T) * (onehot - softmax(h[r] @ w^T / T)), lse being linear_logprob's at that temperature (iadr1_linear_logprob_dlogits_t)."""
     R, K = h.shape
     V = w.shape[0]
     dl = out if out is not None else torch.empty(R, V, dtype=BF16, device=h.device)
-    hip.call("linear_logprob_dlogits", h, w, targets, lse, g, dl, _ld(dl), R, V, K, _ld(h), _ld(w))
+    if temperature == 1.0:
+        hip.call("linear_logprob_dlogits", h, w, targets, lse, g, dl, _ld(dl), R, V, K, _ld(h), _ld(w))
+    else:
+        hip.call("linear_logprob_dlogits_t", h, w, targets, lse, g, dl, _ld(dl), R, V, K, _ld(h), _ld(w), float(temperature))
     return dl
 
 
@@ -650,10 +658,10 @@ _sample_ws = {}     # (B, device) -> the workspace of the first four samplers: i
 
 
 def _sample(name, logits32, temperature, top_k, top_p, seed, step, suppress_token, step_ptr, out, seed_ptr, logp_out=None, want_logp=False, ex=None, guide=None,
-            ent_out=None, want_ent=False):
+            ent_out=None, want_ent=False, logp_temperature=1.0):
     """The work of the five wrappers below.  name: the wrapper's, and from sample_logp onwards (the calls that take logp_out) the library call's; ex: (min_p,
     repetition_penalty, seen, mark_seen) from sample_ex onwards; guide: (state, allow, trans) from sample_guided onwards; ent_out / want_ent: sample_ent's, as logp_out / want_logp.  Returns (ids, logp_out or None), sample_ent
-    (ids, logp_out or None, ent_out or None)."""
+    (ids, logp_out or None, ent_out or None).  logp_temperature other than 1.0 (sample_ent only): iadr1_sample_ent_t."""
     B, V = logits32.shape
     ent = name == "sample_ent"
     key = (B, logits32.device, "ent") if ent else (B, logits32.device)
@@ -678,9 +686,13 @@ def _sample(name, logits32, temperature, top_k, top_p, seed, step, suppress_toke
     assert allow is None or (trans is not None and trans.dim() == 2 and trans.dtype == torch.int16 and trans.stride(1) == 1 and trans.shape[0] == S), f"{name}: trans is [S, >= V] int16"
     assert allow is None or (state is not None and state.dtype == torch.int32 and state.dim() == 1 and state.numel() == B and state.stride(0) == 1), f"{name}: state is [B] int32"
     guide_args = () if guide is None else (state, allow, allow.stride(0) if allow is not None else 0, trans, trans.stride(0) if trans is not None else 0, S)
+    temp_args = ()
+    if logp_temperature != 1.0:
+        assert ent, f"{name}: only sample_ent takes a logp_temperature"
+        name, temp_args = "sample_ent_t", (float(logp_temperature),)
     hip.call("sample_topk_topp" if name == "sample" else name, logits32, _ld(logits32), o, *logp_args, _sample_ws[key], B, V, float(temperature), int(top_k), float(top_p), *ex_args,
              int(suppress_token), int(seed), int(step), step_ptr, seed_ptr, *guide_args, *((ent_out, _ld(ent_out) if ent_out is not None else 0,
-                                                                                            ent_out.shape[1] if ent_out is not None else 0) if ent else ()))
+                                                                                            ent_out.shape[1] if ent_out is not None else 0) if ent else ()), *temp_args)
     return (o, logp_out, ent_out) if ent else (o, logp_out)
 
 
@@ -713,13 +725,14 @@ def sample_guided(logits32, temperature, top_k, top_p, seed, step, state=None, a
 
 
 def sample_ent(logits32, temperature, top_k, top_p, seed, step, state=None, allow=None, trans=None, min_p=0.0, repetition_penalty=1.0, seen=None, mark_seen=False,
-               suppress_token=-1, step_ptr=None, out=None, seed_ptr=None, logp_out=None, want_logp=True, ent_out=None, want_ent=True):
+               suppress_token=-1, step_ptr=None, out=None, seed_ptr=None, logp_out=None, want_logp=True, ent_out=None, want_ent=True, logp_temperature=1.0):
     """iadr1_sample_ent: `sample_guided` plus H = -sum p ln p of softmax(raw row) at temperature 1 -- no suppression, mask, penalty or filter: the distribution
     logp_out is the log-prob under.  ent_out: [B, cols] fp32, written at column step (*step_ptr when given), untouched when that is >= cols; None with want_ent: a
     fresh [B, 1] tensor (step must then be 0 and step_ptr None); None without: sample_guided's own launch.  Ids, logp_out, seen and state are sample_guided's bits.
+    logp_temperature other than 1.0 (iadr1_sample_ent_t): logp_out and ent_out under softmax(raw row / logp_temperature); ids, seen and state do not change.
     Returns (ids, logp_out or None, ent_out or None)."""
     return _sample("sample_ent", logits32, temperature, top_k, top_p, seed, step, suppress_token, step_ptr, out, seed_ptr, logp_out, want_logp,
-                   ex=(min_p, repetition_penalty, seen, mark_seen), guide=(state, allow, trans), ent_out=ent_out, want_ent=want_ent)
+                   ex=(min_p, repetition_penalty, seen, mark_seen), guide=(state, allow, trans), ent_out=ent_out, want_ent=want_ent, logp_temperature=logp_temperature)
 
 
 def seen_init(ids, lengths, G, V, seen):

@@ -422,7 +422,7 @@ class ChunkedRefPass:
 
     def _policy_head(self, rows: torch.Tensor, targets: torch.Tensor, cols: slice, n_ok: int | None = None):
         """log p / log-sum-exp of the policy's lm_head at arena rows `rows` ([N x k], sequence-major; targets < 0: not scored) -> columns `cols` of pol_logp / pol_lse
-        (the first n_ok of the k positions per sequence).  Engine.logprobs' fused launch on other rows: per row the same bits."""
+        (the first n_ok of the k positions per sequence).  Engine.logprobs' fused launch on other rows, at the policy engine's logp_temperature: per row the same bits."""
         pe, tr = self.policy
         W = pe.p.w(pe.p.lm_head_name())
         hsel = ops.embed_fwd(rows, None, tr["hf"], None)
@@ -431,7 +431,7 @@ class ChunkedRefPass:
         ws = self.__dict__.get("_head_ws")
         if ws is None or ws.numel() < need:
             ws = self._head_ws = torch.empty(need, dtype=torch.uint8, device=self.e.dev)
-        lp, ls = ops.linear_logprob(hsel, W, targets, ws=ws)
+        lp, ls = ops.linear_logprob(hsel, W, targets, ws=ws, temperature=pe.logp_temperature)
         k = R // self.N
         n_ok = k if n_ok is None else n_ok
         self.pol_logp[:, cols] = lp.view(self.N, k)[:, :n_ok]

@@ -103,7 +103,7 @@ class Rollout:
         self.decode_events = None   # bench.py sets a list: (start event, end event, decode steps, sum of prompt lengths over sequences) per call
         self.seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self.sampling = dict(temperature=0.9, top_k=50, top_p=0.9, suppress=-1, eos=c.eos_token_id, pad=c.pad_token_id, logps=False, min_p=0.0, repetition_penalty=1.0, guided=False,
-                             entropy=False)
+                             entropy=False, logp_temperature=1.0)
         self.logps = None           # [N, max_new] fp32 log-probs of the sampled tokens (generate(return_logps=True)): column = the step counter, like out_tokens
         self.entropy = None         # [N, max_new] fp32 entropies of the rows the tokens were sampled from (generate(return_entropy=True)): column = the step counter, like logps
         self.seen = None            # [N, ceil(V / 32)] 32-bit words (generate(repetition_penalty != 1)): bit id & 31 of word id >> 5 = the sequence has seen token id
@@ -178,13 +178,15 @@ class Rollout:
 
     def _sample_and_advance(self):
         s = self.sampling
-        if s["entropy"]:
-            # iadr1_sample_ent: whatever of the branches below is live (a guide, the penalty, min_p, the log-probs), plus the raw row's entropy at column *step
+        if s["entropy"] or s["logp_temperature"] != 1.0:
+            # iadr1_sample_ent: whatever of the branches below is live (a guide, the penalty, min_p, the log-probs), plus the raw row's entropy at column *step.
+            # logp_temperature != 1 (set only when log-probs or entropies are asked for): iadr1_sample_ent_t, both under softmax(row / logp_temperature)
             pen = s["repetition_penalty"] != 1.0
             guide = dict(state=self.g_state, allow=self.g_allow, trans=self.g_trans) if s["guided"] else {}
             ops.sample_ent(self.logits, s["temperature"], s["top_k"], s["top_p"], 0, 0, **guide, min_p=s["min_p"], repetition_penalty=s["repetition_penalty"],
                            seen=self.seen if pen else None, mark_seen=pen, suppress_token=s["suppress"], step_ptr=self.step, out=self.sampled, seed_ptr=self.seed_dev,
-                           logp_out=self.logps if s["logps"] else None, want_logp=False, ent_out=self.entropy, want_ent=False)
+                           logp_out=self.logps if s["logps"] else None, want_logp=False, ent_out=self.entropy if s["entropy"] else None, want_ent=False,
+                           logp_temperature=s["logp_temperature"])
         elif s["guided"]:
             # iadr1_sample_guided: the mask of every row's automaton state in front of the filters below, the state moved along the pick inside the second launch
             pen = s["repetition_penalty"] != 1.0
@@ -232,7 +234,7 @@ class Rollout:
 
     def _generate(self, plan: TextPlan, img_embeds, G: int, max_new: int, temperature=0.9, top_k=50, top_p=0.9, seed=0, suppress_eos=False,
                   stop_at_eos=True, train_carry=None, train_trace=False, shadow=None, return_logps=False, min_p=0.0, repetition_penalty=1.0, guide=None,
-                  return_entropy=False):
+                  return_entropy=False, logp_temperature=1.0):
         """plan: the Bp left-padded prompts.  Returns completion ids [Bp*G, max_new] (prompt-major order: p0 x G,
         p1 x G, ...), pad after the first EOS.
         top_k <= 0: the whole vocabulary (top_p must then be 1.0).  return_logps: returns (ids, logps) -- logps [Bp*G, max_new] fp32 on the device, the
@@ -246,6 +248,8 @@ class Rollout:
         return_entropy: the return value gains, at its end, ent [Bp*G, max_new] fp32 on the device -- H = -sum p ln p of softmax(raw logits row) at temperature 1 for
         the row every token was sampled from (iadr1_sample_ent): no suppression, guide mask, penalty or filter, the distribution the log-probs of return_logps are
         taken under; 0 after a sequence's first EOS.  (ids, ent) or (ids, logps, ent).  Ids and log-probs are the bits of a rollout without it.
+        logp_temperature: the log-probs of return_logps and the entropies of return_entropy are taken under softmax(raw row / logp_temperature) (iadr1_sample_ent_t:
+        the quantity Engine.logprobs scores with Engine.logp_temperature set); the ids do not change.  Without either of the two it changes nothing and launches nothing new.
         shadow: an overlap.ChunkedRefPass -- the frozen reference's teacher-forced pass over the tokens produced so far is enqueued on ITS stream every
         `shadow.steps` decode steps, behind one event per chunk (the caller reads shadow.logp after shadow.join())."""
         e, c = self.e, self.e.cfg
@@ -264,6 +268,9 @@ class Rollout:
             raise ValueError(f"min_p must be in [0, 1), got {min_p}")
         if not (np.isfinite(repetition_penalty) and repetition_penalty > 0.0):
             raise ValueError(f"repetition_penalty must be finite and > 0, got {repetition_penalty}")
+        logp_temperature = float(logp_temperature) if (return_logps or return_entropy) else 1.0
+        if not (np.isfinite(logp_temperature) and logp_temperature > 0.0):
+            raise ValueError(f"logp_temperature must be finite and > 0, got {logp_temperature}")
         if guide is not None:
             if suppress_eos:
                 raise ValueError("suppress_eos with a guide: the guide's automaton decides where EOS may appear (exactly where the completion matches); drop one of the two")
@@ -278,7 +285,7 @@ class Rollout:
         sampling = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p),
                         suppress=c.eos_token_id if suppress_eos else -1, eos=c.eos_token_id if stop_at_eos and not suppress_eos else -1, pad=c.pad_token_id,
                         logps=bool(return_logps), min_p=min_p, repetition_penalty=repetition_penalty, guided=guide is not None,
-                        entropy=bool(return_entropy))
+                        entropy=bool(return_entropy), logp_temperature=logp_temperature)
         if repetition_penalty != 1.0 and self.seen is None:
             self.seen = torch.zeros(self.N, (c.vocab_size + 31) // 32, dtype=torch.int32, device=dev)
             self.graph = None          # (the buffer is a kernel argument of the captured sampler)

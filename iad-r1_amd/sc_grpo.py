@@ -56,16 +56,18 @@ class GRPOArgs:
     # of a match of the pattern, EOS only where it matches (iadr1_sample_guided).  Only which ids get sampled changes: the loss, the rollout's log-probs (raw row,
     # no mask) and the training arena are what they are without it.  Not with suppress_eos.
     guide: object | None = None
-    # the rollout also returns the log-prob of every token it sampled (temperature 1, unfiltered: the quantity the loss scores); the step's metrics gain
+    # the rollout also returns the log-prob of every token it sampled (unfiltered, at the temperature the loss scores at -- 1 unless logps_at_temperature: the
+    # quantity the loss scores); the step's metrics gain
     # rollout/logp_abs_diff_mean, rollout/logp_abs_diff_max and rollout/kl against the policy log-probs of the loss.  Nothing in the loss or the gradients changes.
     rollout_logps: bool = False
     # truncated importance weight against the rollout's log-probs (0 = off: the loss does not read them).  cap >= 1: every per-token loss term is multiplied by
     # w = min(exp(scored - sampled), cap), per token ("token") or with the row's mean log-ratio ("sequence"); w is a constant under differentiation
     # (iadr1_grpo_loss_is).  Implies what rollout_logps asks of the rollout; the rollout/* metrics then come from the kernel's partials, plus rollout/is_weight_mean
-    # and rollout/is_clipped_frac.  Corrects the sampler-engine / trainer mismatch only (both sides temperature 1, unfiltered), not the temperature or top-k / top-p.
+    # and rollout/is_clipped_frac.  Corrects the sampler-engine / trainer mismatch only (both sides unfiltered and at the same temperature: 1, or `temperature` with
+    # logps_at_temperature), not top-k / top-p nor, by default, the sampler's temperature.
     rollout_is_cap: float = 0.0
     rollout_is_level: str = "token"
-    # the rollout also returns the entropy of the distribution every token was sampled from (iadr1_sample_ent: softmax of the raw logits row at temperature 1, the
+    # the rollout also returns the entropy of the distribution every token was sampled from (iadr1_sample_ent: softmax of the raw logits row at temperature 1 -- at `temperature` with logps_at_temperature --, the
     # distribution rollout_logps is taken under); the step's metrics gain `entropy` (trl's key), its mean over the live completion tokens.  An APPROXIMATION of
     # trl's number: these are the decode engine's logits under the policy that sampled, not a second forward, and they are fixed per generation where trl
     # recomputes them on every reuse step.  Nothing in the loss or the gradients changes.
@@ -90,6 +92,12 @@ class GRPOArgs:
     # a completion that reached max_completion_length without an EOS drops out of the loss: its row of the loss mask is zeroed (REF ...grpo_trainer.py:983-986), and
     # the step logs completions/clipped_ratio, the share of such rows (REF ...grpo_trainer.py:1105)
     mask_truncated_completions: bool = False
+    # trl's definition of every log-prob (REF trl/trl/trainer/grpo_trainer.py:818-821: logits / temperature before the log-softmax, for the policy, the old policy and
+    # the reference alike).  False: temperature 1, what the reference's trainer computes (sc_grpo_trainer.py:505-513).  True: with T = `temperature`, the policy's and
+    # the reference's log-probs, the cached old_logps, the rollout's log-probs and entropies are all taken under softmax(x / T) (iadr1_linear_logprob_fwd_t /
+    # _dlogits_t, iadr1_sample_ent_t), and with them everything derived: the KL term and metric, the clip ratios, rollout/*, the IS weights, `entropy` and the
+    # top_entropy_quantile threshold.  Which tokens get sampled does not change.  T is `temperature` also on a greedy rollout (the sampler's 0 is its own).
+    logps_at_temperature: bool = False
     learning_rate: float = 1e-6
     weight_decay: float = 0.0
     adam_beta1: float = 0.9
@@ -117,6 +125,11 @@ class GRPOArgs:
     # `--gradient_checkpointing` (REF scripts/train/SC_GRPO/*.sh:56): "off" | "auto" | "on" -- vlm.Engine.recompute_wanted.  With recomputation the policy's
     # forward is run after the rollout (the rollout's own activations are not kept either)
     recompute: str = "off"
+
+    @property
+    def logp_temperature(self) -> float:
+        """The temperature every log-prob and entropy of the step is taken at."""
+        return float(self.temperature) if self.logps_at_temperature else 1.0
 
     @property
     def wants_rollout_logps(self) -> bool:
@@ -472,6 +485,8 @@ class SCGRPOEngine:
     def __init__(self, cfg: VLMConfig, policy: ParamStore, ref: ParamStore | None, args: GRPOArgs, group=None):
         """ref: the frozen reference's store, or None with args.beta == 0 (REF trl/trl/trainer/grpo_trainer.py:407): the step then has no KL term, runs no reference
         pass of any kind (also when a store is given) and takes the sequential structure -- see _shadow_cus."""
+        if args.logps_at_temperature and not (math.isfinite(args.temperature) and args.temperature > 0):
+            raise ValueError(f"GRPOArgs.logps_at_temperature needs a finite temperature > 0 to score at (got temperature = {args.temperature})")
         if args.top_k <= 0 and args.top_p != 1.0:
             raise ValueError(f"GRPOArgs.top_k <= 0 samples the whole vocabulary and needs top_p == 1.0 (got top_p = {args.top_p}): a nucleus over all tokens is not built")
         if args.rollout_is_cap != 0 and not (math.isfinite(args.rollout_is_cap) and args.rollout_is_cap >= 1.0):
@@ -495,6 +510,9 @@ class SCGRPOEngine:
         self.last_rollout_logps = None      # [N, C] device tensor of the last rollout when args.wants_rollout_logps
         self.last_rollout_entropy = None    # [N, C] device tensor of the last rollout when args.wants_rollout_entropy
         self.pol, self.ref = Engine(policy), (Engine(ref) if ref is not None else None)
+        for e in (self.pol, self.ref):      # policy, reference and (through the policy) the cached old_logps score at the same temperature
+            if e is not None:
+                e.logp_temperature = args.logp_temperature
         self.dev = policy.device
         self.reducer = GradReducer(policy, group)
         self.pol.resident_extra = (ref.resident_bytes() if ref is not None else 0) + self.reducer.staging_bytes()       # static inputs of Engine.recompute_wanted("auto")
@@ -573,7 +591,8 @@ class SCGRPOEngine:
                                       top_k=a.top_k, top_p=a.top_p, seed=a.seed + 1000003 * self.opt_step + 7919 * self.accum, suppress_eos=a.suppress_eos,
                                       train_carry=train_carry, train_trace=trace, shadow=shadow, return_logps=a.wants_rollout_logps,
                                       min_p=0.0 if greedy else (a.min_p or 0.0), repetition_penalty=a.repetition_penalty, **({"guide": a.guide} if a.guide is not None else {}),
-                                      **({"return_entropy": True} if a.wants_rollout_entropy else {}))
+                                      **({"return_entropy": True} if a.wants_rollout_entropy else {}),
+                                      **({"logp_temperature": a.logp_temperature} if a.logp_temperature != 1.0 else {}))
         self.last_rollout_logps, self.last_rollout_entropy = None, None
         if a.wants_rollout_entropy:     # (the rollout's tuple ends in the entropies)
             *toks, self.last_rollout_entropy = toks

@@ -67,6 +67,9 @@ class GRPOConfig:
     loss_type: str = "grpo"
     scale_rewards: bool = True
     mask_truncated_completions: bool = False
+    # trl's definition of the log-probs: every log-prob and entropy of the step is taken under softmax(logits / temperature) (GRPOArgs.logps_at_temperature).  Off:
+    # temperature 1, what the reference's trainer computes.
+    logps_at_temperature: bool = False
     learning_rate: float = 1e-6
     weight_decay: float = 0.0
     adam_beta1: float = 0.9
@@ -438,7 +441,7 @@ class SCGRPOTrainer:
             beta=args.beta, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, min_p=args.min_p, repetition_penalty=args.repetition_penalty, guide=self.guide, rollout_logps=args.rollout_logps, rollout_is_cap=args.rollout_is_cap, rollout_is_level=args.rollout_is_level,
             rollout_entropy=args.rollout_entropy, top_entropy_quantile=args.top_entropy_quantile,
             num_iterations=args.num_iterations, epsilon=args.epsilon, epsilon_high=args.epsilon_high, loss_type=args.loss_type, scale_rewards=args.scale_rewards,
-            mask_truncated_completions=args.mask_truncated_completions, learning_rate=args.learning_rate, weight_decay=args.weight_decay,
+            mask_truncated_completions=args.mask_truncated_completions, logps_at_temperature=args.logps_at_temperature, learning_rate=args.learning_rate, weight_decay=args.weight_decay,
             adam_beta1=args.adam_beta1, adam_beta2=args.adam_beta2, adam_epsilon=args.adam_epsilon, max_grad_norm=args.max_grad_norm,
             gradient_accumulation_steps=args.gradient_accumulation_steps, micro_batch_seqs=args.micro_batch_seqs, seed=args.seed,
             # under data parallelism the policy is "auto" even without the flag: it recomputes only where the static budget (which then reserves RCCL's buffers) is tight

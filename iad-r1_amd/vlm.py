@@ -140,6 +140,9 @@ class Engine:
         # shape, with 10 GB of kept logits more; removed.)  Policy and frozen reference run the same launches, so a policy that equals the reference has KL == 0
         # exactly (bit-equal log-probs).
         self._ws = {}
+        # the temperature `logprobs` / `logprobs_backward` score at: log_softmax(lm_head(h) / logp_temperature).  1.0 (the reference's trainer: REF:505-513) is the plain
+        # launch; sc_grpo.SCGRPOEngine sets it with GRPOArgs.logps_at_temperature (trl: REF:trl/trl/trainer/grpo_trainer.py:818-821), sft.py never does.
+        self.logp_temperature = 1.0
 
     def _workspace(self, key, shape, dtype):
         """Persistent scratch (lm_head logit chunks are GBs: re-allocating them per call costs ~100 ms of page mapping)."""
@@ -1082,7 +1085,7 @@ class Engine:
         """logp[r] = log_softmax(lm_head(hf[rows[r]]))[targets[r]]  (targets < 0 -> 0), by one fused linear_logprob launch pair over all R rows (GEMM
         epilogue -> (max, sum exp) per 64-column slice + target logit, then a per-row merge): the [R,V] logits never reach HBM.  `rows` may repeat a hidden row only where `dup` = (sel, dest, group) says so:
         entries rows[sel] all equal dest[group] (shared-prefix layout: the prompt's last token predicts the first token of
-        every completion of its group); the backward sums their gradients.
+        every completion of its group); the backward sums their gradients.  Scored at self.logp_temperature (1.0: the plain launch); the backward uses the forward's.
         precomputed: (logp [R], lse [R]) of exactly these rows / targets, already produced by the same fused launch elsewhere (overlap.ChunkedRefPass._policy_head, on
         the side stream under the rollout): nothing is launched here but the gather of the selected rows, which the backward reads."""
         P = self.p
@@ -1095,7 +1098,7 @@ class Engine:
             ctx = None
             if save:
                 ptr, idx = self.scatter_plan(rows_host if rows_host is not None else rows.cpu().numpy(), hf.shape[0], self.dev)
-                ctx = {"hsel": hsel, "rows": rows, "targets": targets, "lse": lse, "T": hf.shape[0], "scatter": (ptr, idx)}
+                ctx = {"hsel": hsel, "rows": rows, "targets": targets, "lse": lse, "T": hf.shape[0], "scatter": (ptr, idx), "temperature": self.logp_temperature}
             return logp, ctx
         logp = torch.empty(R, dtype=F32, device=self.dev)
         lse = torch.empty(R, dtype=F32, device=self.dev)
@@ -1103,11 +1106,11 @@ class Engine:
         ws = self._ws.get("lm_logprob_ws")
         if ws is None or ws.numel() < need:                     # grow-only: the row count changes from batch to batch
             ws = self._ws["lm_logprob_ws"] = torch.empty(need + need // 4, dtype=torch.uint8, device=self.dev)
-        ops.linear_logprob(hsel, W, targets, logp=logp, lse=lse, ws=ws)
+        ops.linear_logprob(hsel, W, targets, logp=logp, lse=lse, ws=ws, temperature=self.logp_temperature)
         ctx = None
         if save:
             ptr, idx = self.scatter_plan(rows_host if rows_host is not None else rows.cpu().numpy(), hf.shape[0], self.dev)
-            ctx = {"hsel": hsel, "rows": rows, "targets": targets, "lse": lse, "T": hf.shape[0], "scatter": (ptr, idx)}
+            ctx = {"hsel": hsel, "rows": rows, "targets": targets, "lse": lse, "T": hf.shape[0], "scatter": (ptr, idx), "temperature": self.logp_temperature}
         return logp, ctx
 
     def logprobs_backward(self, g: torch.Tensor, ctx) -> torch.Tensor:
@@ -1121,7 +1124,7 @@ class Engine:
         dl_buf = self._workspace("lm_dlogits", (min(R, self.lm_chunk), W.shape[0]), BF16)
         for r0 in range(0, R, self.lm_chunk):
             r1 = min(R, r0 + self.lm_chunk)
-            dl = ops.linear_logprob_dlogits(hsel[r0:r1], W, targets[r0:r1], lse[r0:r1], g[r0:r1], out=dl_buf[: r1 - r0])
+            dl = ops.linear_logprob_dlogits(hsel[r0:r1], W, targets[r0:r1], lse[r0:r1], g[r0:r1], out=dl_buf[: r1 - r0], temperature=ctx["temperature"])
             ops.gemm_nt(dl, WT, out=dhsel[r0:r1])
             ops.gemm_tn_acc(dl, hsel[r0:r1], self.p.g(name), wide=self.wgrad_tn_wide)          # dW_head += dl^T . h  (no [V, n] transposed copy of the logit gradients)
         # scatter back onto the token rows: dhf[t] = sum of the selected rows that read hidden row t (0 for rows nothing read)

@@ -279,6 +279,19 @@ int iadr1_linear_logprob_fwd(const void* H, const void* W, const long long* targ
                              long long ldh, long long ldw, iadr1_stream_t stream);
 int iadr1_linear_logprob_dlogits(const void* H, const void* W, const long long* targets, const float* lse, const float* g, void* dl, long long ldd,
                                  int M, int V, int K, long long ldh, long long ldw, iadr1_stream_t stream);
+/* The same pair at a temperature (REF:trl/trl/trainer/grpo_trainer.py:818-821: trl divides the logits by the sampling temperature before the log-softmax, for the
+ * policy, the old policy and the reference model alike).  With inv_t = 1.0f / temperature, formed once on the host in fp32, and y = x * inv_t:
+ *   iadr1_linear_logprob_fwd_t:      lse[r] = logsumexp(y[r, :]),  logp[r] = y[r, target] - lse[r]  (ignored targets: 0)
+ *   iadr1_linear_logprob_dlogits_t:  dl[r, j] = (g[r] * inv_t) * (onehot(target) - exp(y[r, j] - lse[r])): the extra 1 / T is the chain rule through y; lse is the one
+ *                                    the _t forward returned
+ * The same two kernels, workspace and launches: both epilogues multiply every accumulator element by inv_t once, one fp32 multiply in registers, before anything else
+ * reads it, and the backward takes rg = g[r] * inv_t; everything after that is the plain pair's code on y.  The plain pair passes 1 (a product by 1.0f is exact), so
+ * temperature = 1 gives the plain pair's bits.  Refused on the host before any launch (prefix "linear_logprob_fwd_t:" / "linear_logprob_dlogits_t:"): a temperature
+ * that is not finite or <= 0, and everything the plain pair refuses. */
+int iadr1_linear_logprob_fwd_t(const void* H, const void* W, const long long* targets, float* logp, float* lse, void* workspace, int M, int V, int K,
+                               long long ldh, long long ldw, float temperature, iadr1_stream_t stream);
+int iadr1_linear_logprob_dlogits_t(const void* H, const void* W, const long long* targets, const float* lse, const float* g, void* dl, long long ldd,
+                                   int M, int V, int K, long long ldh, long long ldw, float temperature, iadr1_stream_t stream);
 /* The GRPO loss: five entry points, ONE kernel body and ONE host function behind them (csrc/loss.hip).  Over one rank's [N, C] completion block, mask m,
  * cnt = sum_i m_i, kl_i = exp(d) - d - 1 with d = ref_logp_i - logp_i, the per-token term is  w_i * (-(q_i s_i - beta * kl_i))  and its derivative in logp_i is
  * g_i = w_i * (beta * (1 - exp(ref_logp_i - logp_i)) - q_i s'_i);  w_i is a constant under differentiation, kl and row_kl stay unweighted.  Three forms differ in
@@ -446,6 +459,22 @@ int iadr1_sample_ent(const float* logits, long long ld, long long* out, float* l
                      int mark_seen, int suppress_token, unsigned long long seed, unsigned step, const unsigned* step_ptr,
                      const unsigned long long* seed_ptr, int* state, const unsigned* allow, long long ld_allow, const short* trans,
                      long long ld_trans, int S, float* ent_out, long long ld_ent, int ent_cols, iadr1_stream_t stream);
+/* iadr1_sample_ent_t: iadr1_sample_ent with logp_out and ent_out taken under softmax(x / logp_temperature) of the raw row -- the quantities trl's per-token log-probs
+ * and entropies are (REF:trl/trl/trainer/grpo_trainer.py:818-821), so that a rollout's log-probs compare with scores from iadr1_linear_logprob_fwd_t.
+ *   With inv_tl = 1.0f / logp_temperature (host, fp32): stage 1  s1 = sum exp((x - m1) * inv_tl),  u1 = sum e * d with d = (x - m1) * inv_tl,  m1 stays the raw maximum;
+ *     stage 2  a_c = exp((m1_c - M1) * inv_tl),  lse = M1 * inv_tl + ln S,  U = sum (u1_c + ((m1_c - M1) * inv_tl) * s1_c) * a_c,  H = ln S - U / S;  the pick's
+ *     logp = raw * inv_tl - lse.  Still the raw row: no suppression, mask, penalty or filter -- only the temperature changes.
+ *   logp_temperature touches nothing else: the filter, the whole-vocabulary masses (mT, sT) (the SAMPLING temperature), the Philox draw, `seen` and the automaton read
+ *     what they read in iadr1_sample_ent, so ids, seen and state are bit-equal to that call's.  The older entry points pass inv_tl = 1: logp_temperature = 1 gives
+ *     iadr1_sample_ent's bits on every output.  The same kernels (no template flag of its own) and iadr1_sample_ent's workspace.
+ *   ent_out == NULL && logp_out == NULL is legal: iadr1_sample_ent's launch.
+ *   Refused on the host, before any launch (prefix "sample_ent_t:"): logp_temperature not finite or <= 0, and everything iadr1_sample_ent refuses (the whole-vocabulary
+ *     nucleus included).  Two launches, no allocation, no host sync: legal under hipGraph capture. */
+int iadr1_sample_ent_t(const float* logits, long long ld, long long* out, float* logp_out, long long ld_logp, int logp_cols, void* workspace, int B,
+                       int V, float temperature, int top_k, float top_p, float min_p, float repetition_penalty, unsigned* seen, long long ld_seen,
+                       int mark_seen, int suppress_token, unsigned long long seed, unsigned step, const unsigned* step_ptr,
+                       const unsigned long long* seed_ptr, int* state, const unsigned* allow, long long ld_allow, const short* trans,
+                       long long ld_trans, int S, float* ent_out, long long ld_ent, int ent_cols, float logp_temperature, iadr1_stream_t stream);
 /* iadr1_seen_init: the seen bitmap of a rollout's Bp * G sequences from its Bp left-padded prompts ids [Bp, S]: zeroes rows [0, Bp * G) (ld_seen words each) and,
  * for sequence r, sets the bits of the lengths[r / G] live tokens of prompt row r / G (columns [S - len, S): image placeholder ids included, left padding
  * not).  Ids outside [0, V) are ignored, never written.  One launch; integer atomic OR on global memory. */

@@ -110,6 +110,9 @@ def build_parser():
                    help="false: advantages are reward - group mean, not divided by the group's std")
     p.add_argument("--mask_truncated_completions", nargs="?", default=False, const=True, type=lambda v: str(v).lower() in ("1", "true", "yes"),
                    help="completions that reach --max_completion_length without an EOS leave the loss; logs completions/clipped_ratio")
+    p.add_argument("--logps_at_temperature", nargs="?", default=False, const=True, type=lambda v: str(v).lower() in ("1", "true", "yes"),
+                   help="take every log-prob and entropy of the step (policy, reference, cached old log-probs, the rollout's) under softmax(logits / --temperature), "
+                        "trl's definition; default: temperature 1, the reference trainer's")
     p.add_argument("--learning_rate", type=float, default=1e-6)
     p.add_argument("--weight_decay", type=float, default=0.0)
     p.add_argument("--max_grad_norm", type=float, default=1.0)

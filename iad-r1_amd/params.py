@@ -908,3 +908,36 @@ class ParamStore:
     def copy_from(self, other: "ParamStore"):
         self.flat.copy_(other.flat)
         self.finalize()
+
+    def layout_digest(self) -> str:
+        """Digest of what a flat buffer of this store means: every slot's name, offset and shape, and the total length.  Two stores with the same digest can
+        exchange flat buffers element for element (checkpoints of the training state, mix_from)."""
+        import hashlib
+        h = hashlib.sha1()
+        for name in sorted(self.slots):
+            sl = self.slots[name]
+            h.update(f"{name}:{sl.offset}:{tuple(sl.shape)};".encode())
+        h.update(str(self.n_total).encode())
+        return h.hexdigest()
+
+    def mix_from(self, other: "ParamStore", alpha: float, dist2: torch.Tensor | None = None):
+        """self <- alpha * other + (1 - alpha) * self over the whole flat bf16 buffer, in one launch (iadr1_ref_mix: elements with equal bits stay, one rounding),
+        then this store's derived copies are refreshed.  trl's SyncRefModelCallback with self the reference model and other the policy.
+        dist2: a [2] fp32 device tensor that receives sum (other - self)^2 and sum self^2 over the buffer as it was BEFORE the mix.
+        Stream-ordered on the current stream; `other` is only read.  Refuses a store of a different layout.  A trainable store's fp32 masters are not touched: this
+        is for frozen copies."""
+        from . import hip
+        if other.n_total != self.n_total or other.layout_digest() != self.layout_digest():
+            raise ValueError(f"ParamStore.mix_from: the other store has a different parameter layout ({other.n_total} elements, digest {other.layout_digest()[:12]}; "
+                             f"this one {self.n_total}, {self.layout_digest()[:12]})")
+        if other.flat.device != self.flat.device:
+            raise ValueError(f"ParamStore.mix_from: the two stores live on different devices ({other.flat.device} and {self.flat.device})")
+        scratch = None
+        if dist2 is not None:
+            if dist2.dtype != F32 or dist2.numel() < 2 or dist2.device != self.flat.device or not dist2.is_contiguous():
+                raise ValueError("ParamStore.mix_from: dist2 must be a contiguous fp32 tensor of 2 elements on the store's device")
+            scratch = self.__dict__.get("_mix_partials")
+            if scratch is None:
+                scratch = self._mix_partials = torch.empty(hip.lib().iadr1_ref_mix_partials(), dtype=F32, device=self.flat.device)
+        hip.call("ref_mix", self.flat, other.flat, self.n_total, float(alpha), scratch, dist2)
+        self.refresh_shadows()

@@ -98,6 +98,15 @@ class GRPOArgs:
     # _dlogits_t, iadr1_sample_ent_t), and with them everything derived: the KL term and metric, the clip ratios, rollout/*, the IS weights, `entropy` and the
     # top_entropy_quantile threshold.  Which tokens get sampled does not change.  T is `temperature` also on a greedy rollout (the sampler's 0 is its own).
     logps_at_temperature: bool = False
+    # trl.GRPOConfig's names and defaults (REF trl/trl/trainer/grpo_config.py:369-390; SyncRefModelCallback, REF trl/trl/trainer/callbacks.py:93-131): the TR-DPO
+    # reference update.  After every ref_model_sync_steps-th optimizer step (optimizer_step: the step counter after its increment, every step of a reused rollout
+    # counts) the reference's flat buffer becomes ref_model_mixup_alpha * policy + (1 - alpha) * reference in one launch (ParamStore.mix_from, iadr1_ref_mix); that
+    # step's metrics gain ref/policy_dist, the relative L2 distance |policy - reference| / |reference| before the mix, and ref/syncs, the number of syncs so far.
+    # Reference log-probs a generation cached (num_iterations > 1) stay what they were scored as, as in trl.  Off: the step issues the launches it always has; the
+    # other two fields are then accepted and ignored, as in trl.  Refused with beta == 0 (there is no reference to move; trl silently does nothing).
+    sync_ref_model: bool = False
+    ref_model_mixup_alpha: float = 0.6
+    ref_model_sync_steps: int = 512
     learning_rate: float = 1e-6
     weight_decay: float = 0.0
     adam_beta1: float = 0.9
@@ -206,6 +215,28 @@ def entropy_keep_mask(ent, live, rho: float, group=None):
         return torch.zeros_like(live_d), torch.full((), float("inf"), dtype=F32, device=dev)
     tau = torch.quantile(e_live, 1.0 - rho, interpolation="linear")
     return live_d & (ent32 >= tau), tau
+
+
+def check_sync_ref_args(who: str, sync_ref_model, ref_model_mixup_alpha, ref_model_sync_steps, beta):
+    """sync_ref_model / ref_model_mixup_alpha / ref_model_sync_steps of GRPOArgs and GRPOConfig (`who` names the class in the message).  With sync_ref_model off the
+    other two are not looked at (trl ignores them too)."""
+    if not sync_ref_model:
+        return
+    if beta == 0:
+        raise ValueError(f"{who}.sync_ref_model with beta == 0: there is no reference model to move (no KL term, no frozen copy is built); trl silently does nothing "
+                         "here -- drop sync_ref_model or set beta > 0")
+    al = ref_model_mixup_alpha
+    if isinstance(al, bool) or not isinstance(al, (int, float)) or not (math.isfinite(al) and 0.0 < al <= 1.0):
+        raise ValueError(f"{who}.ref_model_mixup_alpha must be finite and in (0, 1] (got {al!r}): the share of the policy in the new reference; 1 copies the policy")
+    n = ref_model_sync_steps
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"{who}.ref_model_sync_steps must be an integer >= 1 (got {n!r}): the reference moves after every n-th optimizer step")
+
+
+def ref_sync_due(opt_step: int, ref_model_sync_steps: int) -> bool:
+    """trl's on_step_end rule (REF trl/trl/trainer/callbacks.py:127): the reference is mixed at the end of optimizer step number `opt_step` (1-based: the counter
+    after its increment) iff it is a multiple of ref_model_sync_steps."""
+    return opt_step % ref_model_sync_steps == 0
 
 
 LOSS_TYPES = ("grpo", "bnpo", "dr_grpo")
@@ -502,6 +533,7 @@ class SCGRPOEngine:
             raise ValueError("GRPOArgs.guide with suppress_eos: the guide's automaton decides where EOS may appear; drop one of the two")
         check_reuse_args("GRPOArgs", args.num_iterations, args.epsilon, args.epsilon_high)
         check_objective_args("GRPOArgs", args.loss_type, args.mask_truncated_completions, args.suppress_eos)
+        check_sync_ref_args("GRPOArgs", args.sync_ref_model, args.ref_model_mixup_alpha, args.ref_model_sync_steps, args.beta)
         if ref is None and args.beta != 0:
             raise ValueError(f"GRPOArgs.beta = {args.beta} needs the frozen reference's ParamStore (ref=None is legal only with beta == 0: the KL term reads its log-probs)")
         self.cfg, self.args = cfg, args
@@ -523,6 +555,11 @@ class SCGRPOEngine:
         self._shadow = None         # overlap.ChunkedRefPass: the frozen reference's pass over the sampled tokens runs under the rollout (step())
         self.norm2 = torch.zeros(1, dtype=F32, device=self.dev)
         self.norm_scratch = torch.zeros(2048, dtype=F32, device=self.dev)
+        self.ref_syncs = 0          # sync_ref_model: how often the reference has been mixed so far (checkpointed as trainer_state.json's ref_syncs)
+        self._ref_sync = None       # the last sync's record for the step's deferred metrics: (opt_step, pinned [2] host copy of dist2, event behind the copy, ref_syncs)
+        if args.sync_ref_model:
+            self.ref_dist2 = torch.zeros(2, dtype=F32, device=self.dev)
+            self._ref_dist2_host = torch.zeros(2, dtype=F32).pin_memory() if self.dev.type == "cuda" else torch.zeros(2, dtype=F32)
 
     # ---- vision: once per unique image ---------------------------------------------------------------------
     def _vision(self, batch, want_policy_ctx: bool):
@@ -896,10 +933,13 @@ class SCGRPOEngine:
             if tau is not None:
                 means += [tau.to(F32), keep.sum().to(F32) / float(max(1, int(lmask.sum())))]
         dev_means = torch.stack(means)       # one device -> host read for all of them
+        closes_step = self.opt_step + 1      # the optimizer step this call's gradients go into; with deferred metrics it has run by the time they are read
 
         def finalize():
             lk = dev_means.tolist()
             metrics.update(loss=lk[0])
+            if a.sync_ref_model and last_micro_step:
+                metrics.update(self.ref_sync_metrics(closes_step))
             if not no_ref:          # as in trl (REF trl/trl/trainer/grpo_trainer.py:1224): no kl key without a KL term
                 metrics.update(kl=lk[1])
             if use_clip:
@@ -947,11 +987,48 @@ class SCGRPOEngine:
                 hip.call("adamw_flat", st.master[lo:hi], st.m[lo:hi], st.v[lo:hi], st.grad[lo:hi], st.flat[lo:hi], hi - lo, a.learning_rate,
                          a.adam_beta1, a.adam_beta2, a.adam_epsilon, wd, self.opt_step, scale, self.norm2, a.max_grad_norm)
         st.refresh_shadows()
+        if a.sync_ref_model and ref_sync_due(self.opt_step, a.ref_model_sync_steps):
+            self._sync_ref()
         self.accum = 0
         if self.pol.check_ddp_headroom(a.recompute, group=self.reducer.group):
             # the rollout's captured graph and its training-arena views keep the freed arena's blocks alive: drop them too, THEN hand the memory back to the device
             self._rollout = None
             torch.cuda.empty_cache()
+
+    def _sync_ref(self):
+        """reference <- alpha * policy + (1 - alpha) * reference (GRPOArgs.sync_ref_model), enqueued on the optimizer's stream right behind the AdamW launches.
+        Ordering, with no event of its own and no device synchronisation:
+          * behind the AdamW write of pol.flat: the same stream, later in program order;
+          * behind every read of the reference by the step that just ended: the sequential pass ran on this stream; the co-scheduled pass's side stream was joined
+            into it by ChunkedRefPass.finish (`cur.wait_stream(side)`, and the tail ran on `cur`), and step() orders the caller's stream behind `_main_stream`;
+          * ahead of every read by the next step: the sequential pass and the prefill run on this stream (or on `_main_stream`, which step() makes wait for it);
+            the side stream's first work of a rollout, ChunkedRefPass.prompt_phase, waits for the `gate` event Rollout.generate records on the step's stream behind
+            the prefill, and every chunk (gated on the device step counter) is behind prompt_phase in the side stream's own order; the CU-masked decode stream does
+            `wait_stream` on the step's stream before its first replay.  All of those sit behind the mix in the step's stream.
+        Nothing derived from the reference's weights outlives a step: overlap.cu_split reads `ref.p.w("layers.0.gu.w")` once, as the B operand of a timing GEMM
+        whose values do not matter; ChunkedRefPass keeps activations only (the q|k|v rows in `store`, `_img_ref`), rebuilt by every rollout's begin / prompt_phase;
+        Engine caches index plans and buffers, never weights.  The reference log-probs a generation caches (num_iterations > 1) are kept on purpose, as in trl."""
+        a = self.args
+        self.ref.p.mix_from(self.pol.p, a.ref_model_mixup_alpha, self.ref_dist2)
+        self.ref_syncs += 1
+        self._ref_dist2_host.copy_(self.ref_dist2, non_blocking=True)      # read by the step's deferred metrics (loss_and_grads' finalize), behind their own read
+        ev = None
+        if self.dev.type == "cuda":
+            ev = torch.cuda.Event()
+            ev.record()
+        self._ref_sync = (self.opt_step, self._ref_dist2_host, ev, self.ref_syncs)
+
+    def ref_sync_metrics(self, opt_step: int) -> dict:
+        """{"ref/policy_dist", "ref/syncs"} when the optimizer step numbered `opt_step` (1-based) mixed the reference, else {}.  Called where the step's other
+        deferred metrics are read: their device -> host read has already drained the stream the copy of dist2 was enqueued on, so the event is complete."""
+        rec = self._ref_sync
+        if rec is None or rec[0] != opt_step:
+            return {}
+        _, host, ev, count = rec
+        if ev is not None:
+            ev.synchronize()
+        d2, r2 = float(host[0]), float(host[1])
+        return {"ref/policy_dist": math.sqrt(d2 / r2) if r2 > 0 else float("nan"), "ref/syncs": float(count)}
 
     def grad_norm(self) -> float:
         """Global L2 norm of the last optimizer step's (averaged, unclipped) gradient; synchronises the device."""

@@ -25,7 +25,7 @@ import torch
 
 from . import schedule
 from .params import ParamStore, VLMConfig
-from .sc_grpo import GRPOArgs, SCGRPOEngine, check_entropy_args, check_objective_args, check_reuse_args, check_sampler_args
+from .sc_grpo import GRPOArgs, SCGRPOEngine, check_entropy_args, check_objective_args, check_reuse_args, check_sampler_args, check_sync_ref_args
 
 
 @dataclass
@@ -70,6 +70,12 @@ class GRPOConfig:
     # trl's definition of the log-probs: every log-prob and entropy of the step is taken under softmax(logits / temperature) (GRPOArgs.logps_at_temperature).  Off:
     # temperature 1, what the reference's trainer computes.
     logps_at_temperature: bool = False
+    # trl.GRPOConfig's names and defaults: the TR-DPO reference update.  After every ref_model_sync_steps-th optimizer step the frozen reference becomes
+    # ref_model_mixup_alpha * policy + (1 - alpha) * reference (GRPOArgs.sync_ref_model; metrics ref/policy_dist and ref/syncs on those steps).  Every checkpoint-N
+    # then also holds reference.safetensors (2 bytes per parameter), and a run resumed with the option on refuses a checkpoint without it.  Needs beta != 0.
+    sync_ref_model: bool = False
+    ref_model_mixup_alpha: float = 0.6
+    ref_model_sync_steps: int = 512
     learning_rate: float = 1e-6
     weight_decay: float = 0.0
     adam_beta1: float = 0.9
@@ -157,16 +163,6 @@ def average_over_ranks(values: dict) -> dict:
     return {k: float(v) for k, v in zip(keys, t.tolist())}
 
 
-def _layout_digest(store: ParamStore) -> str:
-    import hashlib
-    h = hashlib.sha1()
-    for name in sorted(store.slots):
-        sl = store.slots[name]
-        h.update(f"{name}:{sl.offset}:{tuple(sl.shape)};".encode())
-    h.update(str(store.n_total).encode())
-    return h.hexdigest()
-
-
 def save_training_state(store: ParamStore, path: str, opt_step: int, global_step: int, extra: Optional[dict] = None):
     """What a run needs to continue bit-exactly, next to the HF-layout weights of `save_checkpoint`: the fp32 master weights and both Adam moments
     (flat, in the ParamStore layout) as optimizer.safetensors, and trainer_state.json (global_step, the optimizer's step counter -- bias correction and
@@ -176,9 +172,9 @@ def save_training_state(store: ParamStore, path: str, opt_step: int, global_step
 
     os.makedirs(path, exist_ok=True)
     save_file({"master": store.master.detach().cpu(), "exp_avg": store.m.detach().cpu(), "exp_avg_sq": store.v.detach().cpu()},
-              os.path.join(path, "optimizer.safetensors"), metadata={"format": "pt", "layout": _layout_digest(store)})
+              os.path.join(path, "optimizer.safetensors"), metadata={"format": "pt", "layout": store.layout_digest()})
     with open(os.path.join(path, "trainer_state.json"), "w") as f:
-        json.dump({"global_step": int(global_step), "opt_step": int(opt_step), "layout": _layout_digest(store), "n_total": int(store.n_total), **(extra or {})}, f, indent=2)
+        json.dump({"global_step": int(global_step), "opt_step": int(opt_step), "layout": store.layout_digest(), "n_total": int(store.n_total), **(extra or {})}, f, indent=2)
 
 
 def load_training_state(store: ParamStore, path: str) -> dict:
@@ -188,7 +184,7 @@ def load_training_state(store: ParamStore, path: str) -> dict:
 
     with open(os.path.join(path, "trainer_state.json")) as f:
         state = json.load(f)
-    if state.get("layout") != _layout_digest(store) or state.get("n_total") != store.n_total:
+    if state.get("layout") != store.layout_digest() or state.get("n_total") != store.n_total:
         raise ValueError(f"{path}: optimizer state was written for a different parameter layout")
     with safe_open(os.path.join(path, "optimizer.safetensors"), framework="pt") as sf:
         store.master.copy_(sf.get_tensor("master"))
@@ -197,6 +193,43 @@ def load_training_state(store: ParamStore, path: str) -> dict:
     store.flat.copy_(store.master.to(torch.bfloat16))      # round-to-nearest-even, as the optimizer kernel writes them
     store.refresh_shadows()
     return state
+
+
+REFERENCE_FILE = "reference.safetensors"
+
+
+def save_reference_state(store: ParamStore, path: str):
+    """The moving reference of GRPOConfig.sync_ref_model next to optimizer.safetensors: its bf16 flat buffer (2 bytes per parameter, in the ParamStore layout) with the
+    layout digest the buffer is only valid for in the metadata."""
+    from safetensors.torch import save_file
+
+    os.makedirs(path, exist_ok=True)
+    save_file({"flat": store.flat.detach().cpu()}, os.path.join(path, REFERENCE_FILE), metadata={"format": "pt", "layout": store.layout_digest()})
+
+
+def check_reference_state(path: str) -> str:
+    """The path of a checkpoint's reference.safetensors, or the refusal a run with sync_ref_model needs: without the file it would silently continue against the
+    base checkpoint as its reference."""
+    f = os.path.join(path, REFERENCE_FILE)
+    if not os.path.exists(f):
+        raise ValueError(f"{path}: no {REFERENCE_FILE}: this checkpoint was written without sync_ref_model, and a run resumed with sync_ref_model on would take the "
+                         "base checkpoint for its reference instead of the one it had moved to; resume with the option off, or from a checkpoint written with it")
+    return f
+
+
+def load_reference_state(store: ParamStore, path: str):
+    """Inverse of save_reference_state on a ParamStore of the same layout: restores the flat buffer and refreshes the store's derived copies."""
+    from safetensors import safe_open
+
+    with safe_open(check_reference_state(path), framework="pt") as sf:
+        layout = (sf.metadata() or {}).get("layout")
+        if layout != store.layout_digest():
+            raise ValueError(f"{path}: {REFERENCE_FILE} was written for a different parameter layout (digest {layout}, this model's {store.layout_digest()})")
+        flat = sf.get_tensor("flat")
+    if flat.dtype != torch.bfloat16 or flat.numel() != store.n_total:
+        raise ValueError(f"{path}: {REFERENCE_FILE} holds {flat.numel()} {flat.dtype} elements, this model's reference has {store.n_total} bf16 ones")
+    store.flat.copy_(flat)
+    store.refresh_shadows()
 
 
 def last_checkpoint(output_dir: str) -> Optional[str]:
@@ -357,6 +390,7 @@ class SCGRPOTrainer:
         check_sampler_args("GRPOConfig", args.min_p, args.repetition_penalty)
         check_objective_args("GRPOConfig", args.loss_type)
         check_entropy_args("GRPOConfig", args.top_entropy_quantile)
+        check_sync_ref_args("GRPOConfig", args.sync_ref_model, args.ref_model_mixup_alpha, args.ref_model_sync_steps, args.beta)
         guide_dfa = None
         if args.vllm_guided_decoding_regex is not None:     # a pattern error surfaces here, before any weight is loaded
             from .guide import compile_regex
@@ -441,7 +475,8 @@ class SCGRPOTrainer:
             beta=args.beta, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, min_p=args.min_p, repetition_penalty=args.repetition_penalty, guide=self.guide, rollout_logps=args.rollout_logps, rollout_is_cap=args.rollout_is_cap, rollout_is_level=args.rollout_is_level,
             rollout_entropy=args.rollout_entropy, top_entropy_quantile=args.top_entropy_quantile,
             num_iterations=args.num_iterations, epsilon=args.epsilon, epsilon_high=args.epsilon_high, loss_type=args.loss_type, scale_rewards=args.scale_rewards,
-            mask_truncated_completions=args.mask_truncated_completions, logps_at_temperature=args.logps_at_temperature, learning_rate=args.learning_rate, weight_decay=args.weight_decay,
+            mask_truncated_completions=args.mask_truncated_completions, logps_at_temperature=args.logps_at_temperature,
+            sync_ref_model=args.sync_ref_model, ref_model_mixup_alpha=args.ref_model_mixup_alpha, ref_model_sync_steps=args.ref_model_sync_steps, learning_rate=args.learning_rate, weight_decay=args.weight_decay,
             adam_beta1=args.adam_beta1, adam_beta2=args.adam_beta2, adam_epsilon=args.adam_epsilon, max_grad_norm=args.max_grad_norm,
             gradient_accumulation_steps=args.gradient_accumulation_steps, micro_batch_seqs=args.micro_batch_seqs, seed=args.seed,
             # under data parallelism the policy is "auto" even without the flag: it recomputes only where the static budget (which then reserves RCCL's buffers) is tight
@@ -560,7 +595,7 @@ class SCGRPOTrainer:
                 self._metrics["kl"].append(m["kl"])
             for k in ("rollout/logp_abs_diff_mean", "rollout/logp_abs_diff_max", "rollout/kl", "rollout/is_weight_mean", "rollout/is_clipped_frac",
                       "clip_ratio/low_mean", "clip_ratio/high_mean", "clip_ratio/region_mean", "policy/ratio_mean", "policy/logp_abs_diff_max", "entropy", "entropy/threshold",
-                      "entropy/kept_frac"):
+                      "entropy/kept_frac", "ref/policy_dist", "ref/syncs"):
                 if k in m:
                     self._metrics[k].append(m[k])
             return m["loss"]
@@ -639,11 +674,16 @@ class SCGRPOTrainer:
             ck = last_checkpoint(a.output_dir) if resume_from_checkpoint is True else resume_from_checkpoint
             if ck is None:
                 raise ValueError(f"No valid checkpoint found in output directory ({a.output_dir})")
+            if a.sync_ref_model:
+                check_reference_state(ck)       # refused before anything is loaded: the policy must not be half-restored when the reference cannot be
             st = load_training_state(self.policy, ck)
             if st["global_step"] % a.num_iterations != 0:
                 raise ValueError(f"{ck}: written at optimizer step {st['global_step']}, inside a generation of num_iterations = {a.num_iterations} steps; the cached rollout "
                                  "is not checkpointed, so a run can only resume at a multiple of num_iterations")
             self.engine.opt_step, self.state.global_step, start = st["opt_step"], st["global_step"], st["global_step"]
+            if a.sync_ref_model:        # (off: a checkpoint that has the file resumes as always, against the starting checkpoint)
+                load_reference_state(self.ref, ck)
+                self.engine.ref_syncs = int(st.get("ref_syncs", 0))
         rows = list(self.train_dataset)
         bs, ga = a.per_device_train_batch_size, a.gradient_accumulation_steps
         # prompts are sharded over ranks, each rank keeps whole groups.  Every rank derives the step count from the GLOBAL
@@ -686,7 +726,9 @@ class SCGRPOTrainer:
             if a.save_steps and self.state.global_step % a.save_steps == 0 and rank == 0:
                 ck = os.path.join(a.output_dir, f"checkpoint-{self.state.global_step}")
                 self.save_model(ck)
-                save_training_state(self.policy, ck, self.engine.opt_step, self.state.global_step)
+                save_training_state(self.policy, ck, self.engine.opt_step, self.state.global_step, extra={"ref_syncs": int(self.engine.ref_syncs)} if a.sync_ref_model else None)
+                if a.sync_ref_model:
+                    save_reference_state(self.ref, ck)
         return self.log_history
 
     def save_model(self, output_dir: Optional[str] = None):

@@ -360,6 +360,23 @@ int iadr1_sumsq(const float* g, long long n, float* partials2048, float* out, ia
 int iadr1_adamw_flat(float* master, float* m, float* v, float* grad_zeroed_after, void* param_bf16, long long n, float lr,
                      float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
                      const float* norm2, float max_norm, iadr1_stream_t stream);
+/* iadr1_ref_mix: the TR-DPO reference update of trl's GRPOConfig(sync_ref_model, ref_model_mixup_alpha, ref_model_sync_steps) -- SyncRefModelCallback,
+ * REF:trl/trl/trainer/callbacks.py:107-109 `target_param.data.mul_(1.0 - alpha).add_(copy_param.data, alpha=alpha)` in a loop over the parameters (added to the
+ * trainer at REF:trl/trl/trainer/grpo_trainer.py:666) -- over the flat bf16 parameter buffer, in place in `ref`:
+ *   ref[i] = bf16_rn( fl(c * ref[i]) + fl(a * pol[i]) ),  a = (float)alpha,  c = (float)(1.0 - (double)alpha), formed on the host; fp32 products and sum, never
+ *     contracted, ONE rounding to bf16 (trl's in-place bf16 arithmetic rounds twice, and how depends on the device: the formula is restated, not a backend's rounding).
+ *   An element whose ref and pol hold the same bits keeps them (a select in front of the arithmetic, not a property of the rounding): zero padding and tensors the
+ *     optimizer never moved stay bit-identical.  alpha == 1 copies pol.  pol is read only.
+ *   dist2 (may be NULL): [2] fp32, written by the same pass from the reference BEFORE it is overwritten: dist2[0] = sum (pol - ref)^2, dist2[1] = sum ref^2 (fp32;
+ *     sqrt(dist2[0] / dist2[1]) is the relative L2 distance of the policy from its reference).  Two-stage ordered reduction like iadr1_sumsq, no float atomics,
+ *     run-to-run bit-identical; `partials`: a scratch of iadr1_ref_mix_partials() floats (8192).  Summation depth D = 8 T + ceil(B / 256) + 23 with
+ *     B = min(ceil(n / 2048), 4096) blocks and T = ceil(n / (2048 B)) trips; relative error <= D * 2^-24 (non-negative terms).  With dist2 NULL no partial is written,
+ *     partials may be NULL, and ref gets the same bits.
+ *   One launch of 256-thread blocks, 16-byte loads and stores, grid-stride, grid capped at 4096 blocks like iadr1_adamw_flat (+ a one-block launch with dist2).
+ *   Refused on the host, before any launch (prefix "ref_mix:"): n <= 0; n not a multiple of 8 (no scalar tail: the parameter store's offsets are multiples of 64);
+ *     ref or pol NULL or not 16-byte aligned; alpha not finite or outside (0, 1]; dist2 without partials. */
+int iadr1_ref_mix_partials(void);
+int iadr1_ref_mix(void* ref_bf16, const void* pol_bf16, long long n, float alpha, float* partials, float* dist2, iadr1_stream_t stream);
 
 /* ---- sampler (vLLM SamplingParams(temperature, top_p, top_k), REF:...sc_grpo_trainer.py:353-358) -------------- */
 long long iadr1_sample_workspace_bytes(int B);

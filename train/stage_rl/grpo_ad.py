@@ -113,6 +113,11 @@ def build_parser():
     p.add_argument("--logps_at_temperature", nargs="?", default=False, const=True, type=lambda v: str(v).lower() in ("1", "true", "yes"),
                    help="take every log-prob and entropy of the step (policy, reference, cached old log-probs, the rollout's) under softmax(logits / --temperature), "
                         "trl's definition; default: temperature 1, the reference trainer's")
+    p.add_argument("--sync_ref_model", nargs="?", default=False, const=True, type=lambda v: str(v).lower() in ("1", "true", "yes"),
+                   help="TR-DPO (trl's name): after every --ref_model_sync_steps-th optimizer step the reference model becomes alpha * policy + (1 - alpha) * reference; "
+                        "checkpoints then also hold reference.safetensors. Needs --beta > 0")
+    p.add_argument("--ref_model_mixup_alpha", type=float, default=0.6, help="alpha of --sync_ref_model: the share of the policy in the new reference; in (0, 1], 1 copies the policy")
+    p.add_argument("--ref_model_sync_steps", type=int, default=512, help="optimizer steps between two updates of the reference under --sync_ref_model; >= 1")
     p.add_argument("--learning_rate", type=float, default=1e-6)
     p.add_argument("--weight_decay", type=float, default=0.0)
     p.add_argument("--max_grad_norm", type=float, default=1.0)
